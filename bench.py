@@ -9,6 +9,13 @@ router epsilon drawn on device inside the step, random-init weights (reference i
 
 Multi-GPU: one process per GPU (torchrun), RCCL all-reduce of the flat D/G gradients and the
 [E] expert-load vector; per-GPU batch fixed ("weak" scaling).  Prints ONE JSON line on rank 0.
+
+A plain run does only what the headline figure needs: set up, one eager step that sizes the buffers, capture,
+warm up, the timed steps, the result line.  ``--full`` adds everything else the bench reports: the per-family
+roofline attribution and the live roofline kernel, the CPU baseline and the secondary configs (C5, C4, loop).
+``--dump-outputs DIR`` writes what the last timed step returned as DIR/<name>.npy (dump_outputs below).  Weights
+and inputs are seeded, and with this option the last timed step starts from the seeded initial state again (see
+the timed loop), so two runs, or two builds, can be compared output for output up to one step's rounding.
 """
 import argparse
 import json
@@ -44,10 +51,18 @@ def parse():
                          "configs[4]: 32 experts top-4, MX-fp8 3x3 modulated convs; loop = the C2 workload through the "
                          "drop-in train_aurora_gan loop (pinned host batches, H2D copy included)")
     ap.add_argument("--fp8", action="store_true", help="MX-fp8 3x3 modulated convs (implied by --config C5)")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: the per-family roofline attribution and "
+                         "the live roofline kernel, the CPU baseline, the secondary configs and the process report "
+                         "(each still switched off by its own option below); a plain run skips all of them")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the arrays the last timed step returned to DIR/<name>.npy "
+                         "(float32 / float64; arrays above a size cap as a fixed seeded sample, 64 MB at most in all); "
+                         "that step starts from the seeded initial state, so runs agree up to rounding")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--secondary", default="C5,C4,loop",
                     help="comma-separated configs measured after the headline one, each in a child bench.py process "
-                         "(N=1 only), reported under 'secondary' in the same JSON line; '' to skip")
+                         "(N=1 only), reported under 'secondary' in the same JSON line; '' to skip (--full only)")
     ap.add_argument("--cpu-steps", type=int, default=12, help="timed CPU-oracle steps (B=8; ~10-20 s of CPU work)")
     ap.add_argument("--eager", action="store_true",
                     help="launch every kernel from Python each step instead of replaying the captured hipGraphs")
@@ -58,6 +73,10 @@ def parse():
     ap.add_argument("--one-device", action="store_true",
                     help="map every rank to cuda:0 (multi-rank rehearsal on a 1-GPU box, with --backend gloo)")
     args = ap.parse_args()
+    if not args.full:  # a plain run: the headline figure only
+        args.no_families, args.no_cpu_baseline, args.secondary = True, True, ""
+    if args.dump_outputs and args.config == "loop":
+        ap.error("--dump-outputs: the drop-in loop returns no step outputs; use --config C2 / C4 / C5")
     args.res, args.max_res = 64, 16
     if args.config == "C5":  # BASELINE configs[4]: 64x64, 32 experts top-4, fp8 MFMA conv path, KL + balance
         args.experts, args.topk, args.fp8 = 32, 4, True
@@ -127,7 +146,7 @@ def run_secondary(cfg, args):
     import signal
     import subprocess
     cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--config", cfg, "--steps", str(max(5, args.steps)),
-           "--warmup", str(args.warmup), "--no-cpu-baseline", "--secondary", ""]
+           "--warmup", str(args.warmup), "--full", "--no-cpu-baseline", "--secondary", ""]
     print(f"[bench] secondary config {cfg}: {' '.join(cmd[1:])}", file=sys.stderr, flush=True)
     proc = subprocess.Popen(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, start_new_session=True)
     try:
@@ -262,7 +281,8 @@ def roofline_record(args, B, E, k, families, roof_call, kms, step_ms):
                                      "share_of_step": round(_fam_time(dom) / step_ms, 4)})
     if roof_call is None:
         roof.update({"bound": None, "kernel": None, "achieved": None, "peak": None, "unit": None, "frac": None,
-                     "traffic": None, "note": "no attribution step (--no-families): no roofline kernel"})
+                     "traffic": None, "note": "no attribution step (a plain run, or --no-families): no roofline "
+                                              "kernel; --full measures it"})
         return roof
     fam = roof_call["family"]
     mfma = fam["bound"] == "mfma"
@@ -297,6 +317,49 @@ def roofline_record(args, B, E, k, families, roof_call, kms, step_ms):
                      "traffic": rec.get("traffic_bytes_per_launch"), "rocprof_kernels": rec.get("kernels"),
                      "profile": rec.get("source")})
     return roof
+
+
+def step_state(ts):
+    """Every device tensor a training step reads and updates: parameters, AdamW moments and step counters, the
+    bf16 shadow, the accumulation-window word."""
+    out = []
+    for st in (ts.gs, ts.ds):
+        out += [st.data, st.m, st.v, st.step_dev, st.step_dev_kl] + ([st.shadow] if st.shadow is not None else [])
+    return out + [ts.win]
+
+
+DUMP_CAP = 1 << 19  # elements: a larger array is written as a sample of this many of its elements
+DUMP_LIMIT = 64 * 10 ** 6  # bytes, all files together
+
+
+def dump_outputs(path, out):
+    """Write what the last timed step returned (TrainStep.step's dict: losses, predictions, images, router
+    probabilities and routes, the flat D / G gradients ...) as ``path/<name>.npy``; the tensors of a list entry
+    become ``<name>_<i>``.  Values are float32 (float64 for 64-bit ones; routes and the guard word are small
+    integers, exact in float32).  An array of more than DUMP_CAP elements is written as a 1-D sample of its
+    flattened elements at sorted positions drawn from a CPU generator seeded with the array's size: the same
+    positions in every run and every build."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    flat = {}
+    for name, v in out.items():
+        if torch.is_tensor(v):
+            flat[name] = v
+        elif isinstance(v, (list, tuple)):
+            flat.update({f"{name}_{i}": t for i, t in enumerate(v) if torch.is_tensor(t)})
+    total = 0
+    for name, t in flat.items():
+        t = t.detach()
+        if t.numel() > DUMP_CAP:
+            g = torch.Generator().manual_seed(t.numel())
+            idx = torch.randint(t.numel(), (DUMP_CAP,), generator=g).sort().values
+            t = t.reshape(-1)[idx.to(t.device)]
+        wide = t.dtype in (torch.float64, torch.int64)
+        a = t.to(torch.float64 if wide else torch.float32).cpu().numpy()
+        total += a.nbytes
+        assert total <= DUMP_LIMIT, (name, total)
+        np.save(os.path.join(path, name + ".npy"), a)
+    print(f"[bench] wrote {len(flat)} output arrays ({total / 1e6:.1f} MB) to {path}", file=sys.stderr, flush=True)
 
 
 def reap_children():
@@ -388,6 +451,8 @@ def main():
     eps_d_flat, eps_d = eps_buffers(E, dev)
     eps_g_flat, eps_g = eps_buffers(E, dev)
     perm = torch.empty(B, device=dev, dtype=torch.int32)
+    # --dump-outputs: the dumped (last timed) step starts from this seeded initial state, see the timed loop
+    snap = [t.detach().clone() for t in step_state(ts)] if args.dump_outputs else None
 
     draws = [0]
 
@@ -414,13 +479,16 @@ def main():
         t_f = time.perf_counter()  # first-step host time: allocations + first launch of every kernel (code objects)
         torch.cuda.synchronize()
         t_h = time.perf_counter()
-        graph.run_eager(run_step)  # host enqueue time of one eager step (diagnostic)
-        t_e = time.perf_counter()
-        torch.cuda.synchronize()
         if rank == 0:
             print(f"[bench] first eager step {(t_h - t_w) * 1e3:.1f} ms (host enqueue {(t_f - t_w) * 1e3:.1f} ms: "
-                  f"first-use allocations + code-object loads); second: host enqueue {(t_e - t_h) * 1e3:.1f} ms, "
-                  f"with device {(time.perf_counter() - t_h) * 1e3:.1f} ms", file=sys.stderr, flush=True)
+                  f"first-use allocations + code-object loads)", file=sys.stderr, flush=True)
+        if args.full:
+            graph.run_eager(run_step)  # host enqueue time of one eager step (diagnostic)
+            t_e = time.perf_counter()
+            torch.cuda.synchronize()
+            if rank == 0:
+                print(f"[bench] second eager step: host enqueue {(t_e - t_h) * 1e3:.1f} ms, with device "
+                      f"{(time.perf_counter() - t_h) * 1e3:.1f} ms", file=sys.stderr, flush=True)
 
     # per-family roofline attribution: one eager step (before capture, outside the timed region) with every C-ABI
     # call bracketed by HIP events and its algorithmic work computed from its shape arguments (moegan_mi/roofline.py).
@@ -503,6 +571,18 @@ def main():
     t0 = time.perf_counter()
     step_ev[0].record()
     for i in range(args.steps):
+        if snap is not None and i == args.steps - 1:
+            # The steps before this one trained the model, and training is chaotic: the default kernels' fp32
+            # atomics make two runs differ in the last bits, AdamW turns that into +-lr on parameters whose
+            # gradient is noise, and the near-uniform router of a young model turns those into other top-k routes
+            # (two runs' images were 80 % apart after 25 steps).  So the step whose outputs are written starts from
+            # the seeded initial state, put back here by device copies in stream order (no host wait, once per run),
+            # and draws the first step's router noise: its outputs are a function of the seeds alone, whatever
+            # --steps and --warmup are, up to one step's rounding.
+            draws[0] = 0
+            with torch.no_grad():
+                for t, s in zip(step_state(ts), snap):
+                    t.copy_(s)
         out = one_step()
         step_ev[i + 1].record()
         if rank == 0 and (i + 1) % max(1, args.steps // 4) == 0:
@@ -520,8 +600,10 @@ def main():
         torch.distributed.all_reduce(t, op=torch.distributed.ReduceOp.MAX)
         elapsed = float(t)
     finite = bool(torch.isfinite(out["d_losses"]).all() and torch.isfinite(out["g_gan"]).all())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)
     if rank == 0:
-        arena = ops.fold_arena_bytes(graph.stream if graph is not None else None)
+        arena =ops.fold_arena_bytes(graph.stream if graph is not None else None)
         print(f"[bench] gradient-fold arena: {arena / 2 ** 20:.0f} MiB on the step's stream; torch allocated "
               f"{torch.cuda.memory_allocated(dev) / 2 ** 30:.2f} GiB (peak {torch.cuda.max_memory_allocated(dev) / 2 ** 30:.2f})",
               file=sys.stderr, flush=True)
@@ -596,10 +678,10 @@ def main():
             text = json.dumps(line, separators=(",", ":"))
         sys.stderr.flush()
         print(text, flush=True)
-    left = reap_children()
+    left = reap_children() if args.full else []  # a plain run starts no process
     if left:
         print(f"[bench] ended leftover child processes {left}", file=sys.stderr, flush=True)
-    if rank == 0 and args.config == "C2":
+    if args.full and rank == 0 and args.config == "C2":
         print(f"[bench] other processes of this user at exit: {other_user_processes()}", file=sys.stderr, flush=True)
     if pg is not None:
         torch.distributed.destroy_process_group()

@@ -193,7 +193,7 @@ def test_bench_two_rank_graph_replay():
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2",
            "--master-addr=127.0.0.1", f"--master-port={_free_port()}", os.path.join(REPO, "bench.py"),
            "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8", "--one-device", "--backend", "gloo",
-           "--no-cpu-baseline"]
+           "--full", "--no-cpu-baseline"]  # --full: the attributed step and the live-timed roofline kernel too
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=300, env=env, cwd=REPO)
     assert p.returncode == 0, p.stderr[-3000:]

@@ -44,15 +44,15 @@ for step in "$@"; do
       run 900 ${O}_tests.log python -u -m pytest -x -v -s --timeout 300 --timeout-method thread $files
       grep -E "passed|failed|FAILED" ${O}_tests.log | tail -5 ;;
     bench)
-      run 300 ${O}_bench.log python bench.py --no-cpu-baseline --secondary ""
+      run 300 ${O}_bench.log python bench.py --full --no-cpu-baseline --secondary ""
       grep '^{' ${O}_bench.log > ${O}_bench.json
       cut -c1-400 ${O}_bench.json ;;
     c5bench)
-      run 300 ${O}_c5bench.log python bench.py --config C5 --no-cpu-baseline --secondary ""
+      run 300 ${O}_c5bench.log python bench.py --config C5 --full --no-cpu-baseline --secondary ""
       grep '^{' ${O}_c5bench.log > ${O}_c5bench.json
       cut -c1-400 ${O}_c5bench.json ;;
     fullbench)
-      run 600 ${O}_fullbench.log python bench.py
+      run 600 ${O}_fullbench.log python bench.py --full
       grep '^{' ${O}_fullbench.log > ${O}_fullbench.json
       cut -c1-600 ${O}_fullbench.json ;;
     prof|c5prof)
@@ -60,9 +60,9 @@ for step in "$@"; do
       fargs=""
       cfgname=C2
       [ "$step" = c5prof ] && extra="--config C5" && fargs="256 32 bf16 fp8" && cfgname=C5
-      # with the attribution step (no --no-families): the roofline kernel is chosen, timed and mg_mark-bracketed
+      # with the attribution step (--full, no --no-families): the roofline kernel is chosen, timed and mg_mark-bracketed
       run 400 ${O}_${step}.log rocprofv3 --kernel-trace --stats -d ${O}_${step} -o run --output-format csv -- \
-        python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --secondary "" $extra
+        python3 bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --secondary "" $extra
       grep '^{' ${O}_${step}.log > ${O}_${step}_line.json
       python3 tools/prof_summary.py ${O}_${step}/run_kernel_stats.csv > ${O}_${step}_stats.txt
       FAMILY_LAST=9 python3 tools/family_time.py ${O}_${step}/run_kernel_trace.csv ${O}_${step}_family.json $fargs > ${O}_${step}_family.txt
@@ -72,7 +72,7 @@ for step in "$@"; do
     pmc)
       for c in FETCH_SIZE WRITE_SIZE; do
         run 300 ${O}_pmc_$c.log rocprofv3 --pmc $c -d ${O}_pmc_$c -o run --output-format csv -- \
-          python3 bench.py --steps 2 --warmup 1 --no-cpu-baseline --secondary "" --eager
+          python3 bench.py --steps 2 --warmup 1 --full --no-cpu-baseline --secondary "" --eager
       done
       if [ -f ${O}_prof_line.json ]; then  # the roofline kernel's traffic, bracketed by its mg_mark kernels
         python3 tools/roofline_kernel.py C2 ${O}_prof_line.json ${O}_prof/run_kernel_trace.csv --last 10 \
@@ -102,7 +102,7 @@ for step in "$@"; do
       spec=${step#*tune=}
       cfg=""
       [ "${step%%tune=*}" = c5 ] && cfg="--config C5"
-      run 300 ${O}_tune.log env MOEGAN_TUNE="$spec" python bench.py --no-cpu-baseline --secondary "" $cfg
+      run 300 ${O}_tune.log env MOEGAN_TUNE="$spec" python bench.py --full --no-cpu-baseline --secondary "" $cfg
       grep '^{' ${O}_tune.log > "${O}_${step%%=*}_${spec//[,=]/_}.json"
       echo "${step%%=*} $spec: $(cut -c1-200 "${O}_${step%%=*}_${spec//[,=]/_}.json")" ;;
     *)

@@ -7,7 +7,7 @@ shift
 i=0
 for spec in "$@"; do
   log=gpurun_out/${TAG}_env$i.log
-  timeout -k 10 300 env $spec python bench.py --no-cpu-baseline --secondary "" > $log 2>&1
+  timeout -k 10 300 env $spec python bench.py --full --no-cpu-baseline --secondary "" > $log 2>&1
   rc=$?
   if [ $rc -ne 0 ]; then echo "[gpu_env_ab] '$spec' failed (rc $rc)"; tail -20 $log; exit 1; fi
   echo "[$spec] $(grep '^{' $log | cut -c1-160)"

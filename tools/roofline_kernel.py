@@ -76,7 +76,7 @@ def main():
     roof = line["roofline"]
     launches = bracketed_trace(trace)
     if not launches:
-        raise SystemExit("no bracketed launches in the trace (run bench.py without --no-families)")
+        raise SystemExit("no bracketed launches in the trace (run bench.py --full, without --no-families)")
     sel = launches[-last:] if last else launches[2:] or launches
     avg = sum(d for d, _ in sel) / len(sel)
     kernels = sorted({k for _, ks in sel for k in ks})
