@@ -266,6 +266,12 @@ int mg_attn_fwd(int dtype, const void* qkv, int B, int L, int C, int heads, void
 /* Self-attention backward -> gqkv [B*L, 3C]. */
 int mg_attn_bwd(int dtype, int gout_dtype, const void* qkv, const void* out, const void* gout, const float* lse, int B, int L, int C, int heads, void* gqkv, void* stream);
 
+/* Text cross-attention core (8 heads) for a multi-token text sequence: q [B*Lq, C] (pitch ldq), kv [B*Lk, 2C] (k | v, pitch ldkv), out [B*Lq, C], lse [B, heads, Lq]; key_len (device int32 [B] or NULL): keys j >= key_len[b] are masked. Lk <= 128, Lq <= 1024. t2i_moe_gan.py:549-556. */
+int mg_xattn_fwd(int dtype, const void* q, int64_t ldq, const void* kv, int64_t ldkv, const int32_t* key_len, int B, int Lq, int Lk, int C, int heads, void* out, float* lse, void* stream);
+
+/* Text cross-attention backward -> gq [B*Lq, C], gkv [B*Lk, 2C] (written, masked key rows exactly 0); no atomics, bit-reproducible. */
+int mg_xattn_bwd(int dtype, int gout_dtype, const void* q, int64_t ldq, const void* kv, int64_t ldkv, const int32_t* key_len, const void* out, const void* gout, const float* lse, int B, int Lq, int Lk, int C, int heads, void* gq, void* gkv, void* stream);
+
 /* Head text-branch backward: g_tpre, dW2 text rows (all taps). */
 int mg_d_text_bwd(const float* g_tb, const float* t, const float* w2sum, int B, int Ct, int cofs, float* g_tpre, float* dW2, void* stream);
 

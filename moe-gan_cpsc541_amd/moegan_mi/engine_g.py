@@ -626,7 +626,11 @@ class GeneratorEngine:
     # ------------------------------------------------------------------
     # AttentionBlock  (t2i_moe_gan.py:493-576)
     # ------------------------------------------------------------------
-    def attn_fwd(self, pre, x, w, text_seq, eps, anneal, train=True, save=True, kl_out=None):
+    def attn_fwd(self, pre, x, w, text_seq, eps, anneal, train=True, save=True, kl_out=None, key_len=None):
+        """``text_seq`` [B, 512]: the one-token sequence (cross-attention collapsed algebraically); [B, Lk, 512]
+        (with an optional ``key_len`` int32 [B] padding mask): the multi-token branch (_attn_fwd_seq)."""
+        if text_seq.dim() == 3:
+            return self._attn_fwd_seq(pre, x, w, text_seq, eps, anneal, train, save, kl_out, key_len)
         B, H, W, C = x.shape
         L_ = H * W
         T = B * L_
@@ -666,6 +670,8 @@ class GeneratorEngine:
         return out, probs, kl2, topi, sv
 
     def attn_bwd(self, pre, sv, g_out, gx, gw, g_text_seq, coef=None, kl_coef=None, g_probs=None):
+        if "kv" in sv:  # saved by the multi-token forward; g_text_seq is [B, Lk, 512] there
+            return self._attn_bwd_seq(pre, sv, g_out, gx, gw, g_text_seq, coef, kl_coef, g_probs)
         B, L_ = sv["B"], sv["L"]
         T, C = sv["xf0"].shape
         g_xpre = torch.empty(T, C, device=self.dev, dtype=self.cdt)
@@ -702,6 +708,118 @@ class GeneratorEngine:
             self._flush_xattn_bwd()
 
     # ------------------------------------------------------------------
+    # AttentionBlock with a multi-token text sequence [B, Lk, 512] (t2i_moe_gan.py:525-555 as written: the
+    # softmax over Lk keys is real, so norm2 and the q / k rows of cross_attn.in_proj are live).  Used by the
+    # module API and the generator's autograd path; the fused training step feeds one pooled token and never
+    # comes here.
+    # ------------------------------------------------------------------
+    def _xattn_kv(self, pre, rows, C):
+        """tp = text_proj(text rows) [B*Lk, C] (fp32) and its packed key | value projections kv [B*Lk, 2C] in the
+        compute dtype: functions of the text and the weights only."""
+        tp = ops.linear(rows, self.P(pre + "text_proj.weight"), bias=self.P(pre + "text_proj.bias"))
+        kv = ops.linear(tp, self.P(pre + "cross_attn.in_proj_weight")[C:],
+                        bias=self.P(pre + "cross_attn.in_proj_bias")[C:], out_dtype=self.cdt)
+        return tp, kv
+
+    def _xattn_seq_chain(self, text_seq):
+        """(tp, kv) of every attention block for a token sequence [B, Lk, 512], computed with the prefix."""
+        rows = text_seq.reshape(-1, text_seq.shape[-1])
+        chain = {}
+        for name in self.attn_blocks:
+            p = name + ".attn_block."
+            tp, kv = self._xattn_kv(p, rows, self.P(p + "text_proj.weight").shape[0])
+            chain[p] = dict(tp=tp, kv=kv)
+        return chain
+
+    def _attn_fwd_seq(self, pre, x, w, text_seq, eps, anneal, train, save, kl_out, key_len):
+        B, H, W, C = x.shape
+        L_ = H * W
+        T = B * L_
+        Lk = text_seq.shape[1]
+        rows = text_seq.reshape(B * Lk, text_seq.shape[2])
+        xf0, sv_in = self.mc_fwd(pre + "proj_in.", x, w, save=save)
+        xf0 = xf0.view(T, C)
+        n1, mu1, rs1 = ops.layernorm_fwd(xf0, self.P(pre + "norm1.weight"), self.P(pre + "norm1.bias"))
+        qkv = ops.linear(n1, self.Pc(pre + "self_attn.in_proj_weight"), bias=self.P(pre + "self_attn.in_proj_bias"))
+        att, lse = ops.attn_fwd(qkv, B, L_, C)
+        bv = self._bv.get(pre) if self._bv is not None else None
+        if bv is not None and "kv" in bv:
+            tp, kv = bv["tp"], bv["kv"]
+        else:
+            tp, kv = self._xattn_kv(pre, rows, C)
+        xf_s = ops.linear(att, self.Pc(pre + "self_attn.out_proj.weight"), bias=self.P(pre + "self_attn.out_proj.bias"),
+                          resid=xf0, ld_res=C)
+        n2, mu2, rs2 = ops.layernorm_fwd(xf_s, self.P(pre + "norm2.weight"), self.P(pre + "norm2.bias"))
+        q = ops.linear(n2, self.Pc(pre + "cross_attn.in_proj_weight")[:C],
+                       bias=self.P(pre + "cross_attn.in_proj_bias")[:C])
+        o, lse2 = ops.xattn_fwd(q, kv, B, L_, Lk, C, key_len=key_len)
+        xf1 = ops.linear(o, self.Pc(pre + "cross_attn.out_proj.weight"), bias=self.P(pre + "cross_attn.out_proj.bias"),
+                         resid=xf_s, ld_res=C)
+        n3, mu3, rs3 = ops.layernorm_fwd(xf1, self.P(pre + "norm3.weight"), self.P(pre + "norm3.bias"))
+        s_out = self._batched_style(pre + "proj_out.", C)
+        if s_out is not None and (L_ & (L_ - 1)) == 0:  # proj_out's x * s written by the combine itself
+            xpre, probs, kl2, topi, sv_moe, xs_out = self.moe_fwd(pre + "moe.", n3, xf1, w, L_, eps, anneal, train,
+                                                                  save, kl_out=kl_out, out_style=s_out)
+            xs_out = xs_out.view(B, H, W, C)
+        else:
+            xpre, probs, kl2, topi, sv_moe = self.moe_fwd(pre + "moe.", n3, xf1, w, L_, eps, anneal, train, save,
+                                                          kl_out=kl_out)
+            xs_out = None
+        out, sv_out = self.mc_fwd(pre + "proj_out.", xpre.view(B, H, W, C), w, save=save, xs=xs_out)
+        sv = None
+        if save:
+            sv = dict(sv_in=sv_in, xf0=xf0, n1=n1, mu1=mu1, rs1=rs1, qkv=qkv, att=att, lse=lse, tp=tp, kv=kv,
+                      xf_s=xf_s, n2=n2, mu2=mu2, rs2=rs2, q=q, o=o, lse2=lse2, key_len=key_len, rows=rows, Lk=Lk,
+                      xf1=xf1, n3=n3, mu3=mu3, rs3=rs3, sv_moe=sv_moe, sv_out=sv_out, text_seq=text_seq, B=B, L=L_)
+        return out, probs, kl2, topi, sv
+
+    def _attn_bwd_seq(self, pre, sv, g_out, gx, gw, g_text_seq, coef, kl_coef, g_probs):
+        B, L_, Lk = sv["B"], sv["L"], sv["Lk"]
+        T, C = sv["xf0"].shape
+        g_xpre = torch.empty(T, C, device=self.dev, dtype=self.cdt)
+        self.mc_bwd(pre + "proj_out.", sv["sv_out"], g_out, g_xpre, gw)
+        g_n3 = torch.empty(T, C, device=self.dev, dtype=self.cdt)
+        self.moe_bwd(pre + "moe.", sv["sv_moe"], g_xpre, g_n3, gw, coef=coef, kl_coef=kl_coef, g_probs=g_probs)
+        g_xf1 = g_xpre  # residual path, accumulate LN3 backward into it
+        ops.layernorm_bwd(g_n3, sv["xf1"], sv["mu3"], sv["rs3"], self.P(pre + "norm3.weight"), g_xf1,
+                          self.G(pre + "norm3.weight"), self.G(pre + "norm3.bias"), accumulate=1)
+        # cross-attention: out_proj -> softmax(q k^T) v -> q projection -> LN2 (query side)
+        g_o = ops.linear_dgrad(g_xf1, self.Pc(pre + "cross_attn.out_proj.weight"))
+        ops.linear_wgrad(g_xf1, sv["o"], self.G(pre + "cross_attn.out_proj.weight"))
+        ops.colsum(g_xf1, self.G(pre + "cross_attn.out_proj.bias"))  # (at once: g_xf1 is accumulated into below)
+        g_q, g_kv = ops.xattn_bwd(sv["q"], sv["kv"], sv["o"], g_o, sv["lse2"], B, L_, Lk, C, key_len=sv["key_len"])
+        gWi, gbi = self.G(pre + "cross_attn.in_proj_weight"), self.G(pre + "cross_attn.in_proj_bias")
+        g_n2 = ops.linear_dgrad(g_q, self.Pc(pre + "cross_attn.in_proj_weight")[:C])
+        ops.linear_wgrad(g_q, sv["n2"], gWi[:C])
+        ops.colsum(g_q, gbi[:C])
+        g_xfs = g_xf1  # residual path, accumulate LN2 backward into it
+        ops.layernorm_bwd(g_n2, sv["xf_s"], sv["mu2"], sv["rs2"], self.P(pre + "norm2.weight"), g_xfs,
+                          self.G(pre + "norm2.weight"), self.G(pre + "norm2.bias"), accumulate=1)
+        # key / value side: B * Lk text rows, fp32 like the other per-image chains
+        g_kv32 = g_kv if g_kv.dtype == torch.float32 else ops.cast(g_kv, torch.float32)
+        ops.linear_wgrad(g_kv32, sv["tp"], gWi[C:])
+        ops.colsum(g_kv32, gbi[C:])
+        g_tp = ops.linear_dgrad(g_kv32, self.P(pre + "cross_attn.in_proj_weight")[C:])
+        ops.linear_wgrad(g_tp, sv["rows"], self.G(pre + "text_proj.weight"))
+        ops.colsum(g_tp, self.G(pre + "text_proj.bias"))
+        ops.linear_dgrad(g_tp, self.P(pre + "text_proj.weight"), out=g_text_seq.view(B * Lk, -1), accumulate=1)
+        # self-attention
+        g_att = ops.linear_dgrad(g_xfs, self.Pc(pre + "self_attn.out_proj.weight"))
+        ops.linear_wgrad(g_xfs, sv["att"], self.G(pre + "self_attn.out_proj.weight"))
+        ops.colsum(g_xfs, self.G(pre + "self_attn.out_proj.bias"))
+        g_qkv = ops.attn_bwd(sv["qkv"], sv["att"], g_att, sv["lse"], B, L_, C)
+        g_n1 = ops.linear_dgrad(g_qkv, self.Pc(pre + "self_attn.in_proj_weight"))
+        gWqkv, gbqkv = self.G(pre + "self_attn.in_proj_weight"), self.G(pre + "self_attn.in_proj_bias")
+        self.side.run(lambda: (ops.linear_wgrad(g_qkv, sv["n1"], gWqkv), ops.colsum(g_qkv, gbqkv, defer=True)), g_qkv)
+        g_xf0 = g_xfs
+        ops.layernorm_bwd(g_n1, sv["xf0"], sv["mu1"], sv["rs1"], self.P(pre + "norm1.weight"), g_xf0,
+                          self.G(pre + "norm1.weight"), self.G(pre + "norm1.bias"), accumulate=1)
+        self.mc_bwd(pre + "proj_in.", sv["sv_in"], g_xf0, gx, gw)
+        if not self._defer:  # called on its own: complete this block's gradients now
+            self._flush_router_bwd()
+            self._flush_xattn_bwd()
+
+    # ------------------------------------------------------------------
     # AuroraGenerator  (t2i_moe_gan.py:762-855)
     # ------------------------------------------------------------------
     def _mapping(self, zt, save):
@@ -712,17 +830,21 @@ class GeneratorEngine:
             hs.append(h)
         return h, hs
 
-    def _prefix_fwd(self, z, text, psi, save):
+    def _prefix_fwd(self, z, text, psi, save, text_tokens=None, text_len=None):
         """The part of the forward that does not depend on the router samples: text projection, mapping,
         truncation, every style / demodulation, the constant and gen_block_4's convolution block.  Given the
         same z, text and weights it is identical in the D-phase and G-phase forwards of one step
-        (t2i_moe_gan.py:1288-1296 and :1351-1357 feed the same z; G is not updated in between)."""
+        (t2i_moe_gan.py:1288-1296 and :1351-1357 feed the same z; G is not updated in between).
+        ``text_tokens`` [B, Lk, 512] (with an optional ``text_len`` int32 [B]): the text sequence the attention
+        blocks attend over is text_projection applied per token instead of the one projected pooled row (:790);
+        the pooled ``text`` still feeds the mapping network."""
         B = z.shape[0]
         dev = self.dev
         if text.shape[0] != B and text.shape[0] == 1:
             text = text.expand(B, -1).contiguous()
         # text projection (:682-687, :790)
-        text_c = self._p(text)
+        Lk = None if text_tokens is None else text_tokens.shape[1]
+        text_c = self._p(text if Lk is None else text_tokens.reshape(B * Lk, -1))  # (B * Lk rows with tokens)
         t0 = ops.linear(text_c, self.Pp("text_projection.0.weight"), bias=self.P("text_projection.0.bias"),
                         out_dtype=torch.float32)
         t1, tmu, trs = ops.layernorm_fwd(t0, self.P("text_projection.1.weight"), self.P("text_projection.1.bias"),
@@ -767,22 +889,29 @@ class GeneratorEngine:
         name0, _, _, _, up0, _ = self.blocks[0]
         assert not up0
         x0, cbsv0 = self.cb_fwd(name0 + ".conv_block.", x, w, save=save)
-        xchain = self._xattn_chain(text_seq) if self.attn_blocks else {}
-        return dict(B=B, text=text, text_c=text_c, t0=t0, t1=t1, t1c=t1c, tmu=tmu, trs=trs, text_seq=text_seq,
+        if Lk is not None:
+            text_seq = text_seq.view(B, Lk, -1)
+            xchain = self._xattn_seq_chain(text_seq)
+        else:
+            xchain = self._xattn_chain(text_seq) if self.attn_blocks else {}
+        return dict(B=B, Lk=Lk, text_len=text_len, text=text, text_c=text_c, t0=t0, t1=t1, t1c=t1c, tmu=tmu, trs=trs, text_seq=text_seq,
                     hs=hs, h3=h3, w=w, w_c=w_c, psi=psi, S=S, S2=S2, D=D, x0=x0, cbsv0=cbsv0, save=save,
                     xchain=xchain)
 
     def forward(self, z, text, eps, anneal=1.0, psi=0.7, train=True, save=True, want_img8=False, want_kl=True,
-                keep_prefix=False, prefix=None):
+                keep_prefix=False, prefix=None, text_tokens=None, text_len=None):
         """Returns (img [B,R,R,8] padded NHWC, the intermediate R/2 image or None, kl2 list, probs list, ctx);
         R = max_res (16: the reference generator, img16 / img8).  kl2 / probs / eps: one per attention block.
         ``want_kl=False`` skips the routers' KL terms (their kl2 entries are None).
         ``keep_prefix=True`` computes the router-independent prefix (``_prefix_fwd``) with its saved
         activations and returns it as ``self.last_prefix``; ``prefix=`` reuses such a prefix (same z, text,
-        psi and weights) instead of recomputing it."""
+        psi and weights) instead of recomputing it.
+        ``text_tokens`` [B, Lk, 512] / ``text_len`` int32 [B]: per-token text features for the attention blocks'
+        cross-attention (keys j >= text_len[b] masked); training with them goes through the modules' autograd
+        path (the fused step and the reference dataset carry pooled embeddings only)."""
         self._want_kl = want_kl
         if prefix is None:
-            prefix = self._prefix_fwd(z, text, psi, save or keep_prefix)
+            prefix = self._prefix_fwd(z, text, psi, save or keep_prefix, text_tokens, text_len)
         else:
             assert prefix["B"] == z.shape[0] and prefix["psi"] == psi and (prefix["save"] or not save)
             self._S, self._S2, self._D = prefix["S"], prefix["S2"], prefix["D"]
@@ -818,7 +947,8 @@ class GeneratorEngine:
             if attn:
                 x, p, kl2, topi, asv = self.attn_fwd(name + ".attn_block.", x, w, text_seq,
                                                      None if eps is None else eps[ai], anneal, train, save,
-                                                     kl_out=None if klbuf is None else klbuf[ai])
+                                                     kl_out=None if klbuf is None else klbuf[ai],
+                                                     key_len=prefix["text_len"])
                 ai += 1
                 probs.append(p)
                 kl2s.append(kl2)
@@ -832,7 +962,7 @@ class GeneratorEngine:
         ctx = None
         if save:
             ctx = {k: prefix[k] for k in ("B", "text", "text_c", "t0", "t1", "t1c", "tmu", "trs", "text_seq", "hs",
-                                          "h3", "w", "w_c", "psi")}
+                                          "h3", "w", "w_c", "psi", "Lk")}
             ctx.update(z=z, blocks=blocks, rgbsv=rgbsv, rgb8sv=rgb8sv)
         self.last_klbuf = klbuf  # kl2s are its rows (TrainStep reads the buffer instead of stacking them)
         return img16, img8, kl2s, probs, topis, ctx
@@ -840,11 +970,13 @@ class GeneratorEngine:
     def backward(self, ctx, g_img16, coef=None, kl_coef=None, want_input_grads=False, g_probs=None, g_img8=None):
         """Accumulate all generator parameter gradients for d loss / d img16 (+ balance coef on the last
         router, + KL coefficients [3] per router).  Optional: per-router d loss / d probs [T, E] (g_probs list)
-        and d loss / d img8 (needs forward(..., want_img8=True, save=True)).  Returns (gz, gtext) if requested."""
+        and d loss / d img8 (needs forward(..., want_img8=True, save=True)).  Returns (gz, gtext) if requested;
+        after a forward with ``text_tokens``, (gz, gtext, gtokens [B, Lk, 512])."""
         B = ctx["B"]
         dev = self.dev
+        Lk = ctx["Lk"]  # None: pooled text only
         gw = ops.zeros(B, 512, device=dev)
-        g_ts = ops.zeros(B, 512, device=dev)
+        g_ts = ops.zeros(B if Lk is None else B * Lk, 512, device=dev)
         self._router_bwd, self._xattn_bwd = [], []
         self._defer = True  # per-block small GEMMs are batched over the blocks after the block loop
         if self.style_cols:
@@ -934,9 +1066,11 @@ class GeneratorEngine:
         ops.linear_wgrad(self._p(g_t0), ctx["text_c"], self.G("text_projection.0.weight"))
         ops.colsum(g_t0, self.G("text_projection.0.bias"), defer=True)
         if not want_input_grads:
-            return None, None
+            return (None, None) if Lk is None else (None, None, None)
         gtext = ops.linear_dgrad(g_t0, self.P("text_projection.0.weight"))
         zd = ctx["z"].shape[1]
         gz = g_zt[:, :zd].float().contiguous()
+        if Lk is not None:  # the projection saw the tokens; the pooled text reaches the mapping network only
+            return gz, g_zt[:, zd:].float().contiguous(), gtext.view(B, Lk, -1)
         gtext = gtext + g_zt[:, zd:].float()
         return gz, gtext

@@ -459,26 +459,51 @@ class SparseMoE(_EngineModule):
 # ---------------------------------------------------------------------------
 # AttentionBlock (t2i_moe_gan.py:493-576)
 # ---------------------------------------------------------------------------
-def _text_rows(text_seq):
+def _text_rows(text_seq, text_len=None):
+    """The engine's text operand: [B, 512] for a one-token sequence without a mask (the collapsed path), else the
+    sequence itself [B, Lk, 512] (the multi-token cross-attention branch)."""
     ts = text_seq
-    if ts.dim() == 3:
-        if ts.shape[1] != 1:
-            raise NotImplementedError("AttentionBlock: a one-token text sequence (the generator's text_seq)")
+    if ts.dim() == 3 and ts.shape[1] == 1 and text_len is None:
         ts = ts[:, 0]
+    elif ts.dim() == 2 and text_len is not None:
+        ts = ts[:, None]
     return ts.float().contiguous()
+
+
+def _key_len(text_len, B, Lk, device=None):
+    """``text_len`` (list or int tensor, one entry per image) validated on the host for 1 <= len <= Lk and moved to
+    ``device`` as int32; None stays None (no padding mask: the reference's parity mode)."""
+    if text_len is None:
+        return None
+    tl = torch.as_tensor(text_len).detach().cpu().reshape(-1)
+    if tl.dtype.is_floating_point or tl.dtype == torch.bool:
+        raise ValueError("text_len: integer lengths")
+    if tl.numel() != B:
+        raise ValueError(f"text_len: {B} lengths (one per image), got {tl.numel()}")
+    if int(tl.min()) < 1 or int(tl.max()) > Lk:
+        raise ValueError(f"text_len: every length must be in [1, {Lk}], got {tl.tolist()}")
+    tl = tl.to(torch.int32)
+    return tl if device is None else tl.to(device)
+
+
+def _seq_len(text_seq):
+    return text_seq.shape[1] if text_seq.dim() == 3 else 1
 
 
 class _AttnFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, flat, x, w, text_seq, mod, anneal, train):
+    def forward(ctx, flat, x, w, text_seq, mod, anneal, train, text_len=None):
+        key_len = _key_len(text_len, x.shape[0], _seq_len(text_seq))  # (host check before any device work)
         eng = mod._engine()
         eng.prep()
         xh = _nhwc(x, mod._cdt)
-        ts = _text_rows(text_seq)
+        ts = _text_rows(text_seq, text_len)
+        if key_len is not None:
+            key_len = key_len.to(x.device)
         eps = mod._eps("moe.router.") if train else None
         eng._want_kl = True
         out, probs, kl2, topi, sv = eng.attn_fwd(mod._IPRE, xh, w.float().contiguous(), ts, eps, anneal, train,
-                                                 save=train)
+                                                 save=train, key_len=key_len)
         ctx.mod, ctx.sv, ctx.kl2, ctx.xshape, ctx.tshape = mod, sv, kl2, xh.shape, text_seq.shape
         kl = kl2[0].clone() if train else torch.zeros((), device=x.device)
         if not train:
@@ -496,18 +521,22 @@ class _AttnFn(torch.autograd.Function):
         B = ctx.xshape[0]
         gx = torch.empty(ctx.xshape, device=dev, dtype=mod._cdt)
         gw = torch.zeros(B, ctx.sv["sv_moe"]["w"].shape[1], device=dev)
-        g_ts = torch.zeros(B, ctx.sv["text_seq"].shape[1], device=dev)
+        g_ts = torch.zeros(ctx.sv["text_seq"].shape, device=dev)
         kl_coef = None if g_kl is None else (g_kl.float().reshape(1) * ctx.kl2[1:2]).contiguous()
         gp = None if g_probs is None else g_probs.float().contiguous()
         eng.attn_bwd(mod._IPRE, ctx.sv, _nhwc(g_out, mod._cdt), gx, gw, g_ts, kl_coef=kl_coef, g_probs=gp)
-        return mod._grad_out(), gx.permute(0, 3, 1, 2).float(), gw, g_ts.view(ctx.tshape), None, None, None
+        return mod._grad_out(), gx.permute(0, 3, 1, 2).float(), gw, g_ts.view(ctx.tshape), None, None, None, None
 
 
 class AttentionBlock(_EngineModule):
-    """Reference :493-576: proj_in -> LN -> 8-head self-attention -> LN -> cross-attention against the one-token
-    text sequence (collapsed algebraically: softmax over one key is 1) -> LN -> SparseMoE -> residual ->
-    proj_out.  forward(x, w, text_seq, kl_losses=None, annealing_factor) -> (x_out, routing_probs); the router's
-    KL is appended to ``kl_losses`` as in the reference."""
+    """Reference :493-576: proj_in -> LN -> 8-head self-attention -> LN -> cross-attention against the text
+    sequence -> LN -> SparseMoE -> residual -> proj_out.  ``text_seq`` is [B, Lk, text_dim] with 1 <= Lk <= 128
+    (a one-token sequence is collapsed algebraically: softmax over one key is 1; more tokens run the
+    cross-attention kernels).  forward(x, w, text_seq, kl_losses=None, annealing_factor, text_len=None) ->
+    (x_out, routing_probs); the router's KL is appended to ``kl_losses`` as in the reference.  ``text_len`` (list
+    or int tensor [B], 1 <= len <= Lk) masks the keys past each image's length (key_padding_mask of a right-padded
+    token sequence; the reference passes none).  Training with token sequences goes through this autograd path:
+    the fused TrainStep feeds the pooled embedding only."""
     _IPRE = "b.attn_block."
 
     def __init__(self, dim, text_dim=512, heads=8, num_experts=4, topk=None, latent_dim=LATENT_DIM, dtype="fp32",
@@ -519,8 +548,9 @@ class AttentionBlock(_EngineModule):
         self.dim, self.heads, self.scale = dim, heads, (dim // heads) ** -0.5
         self.num_experts = num_experts
 
-    def forward(self, x, w, text_seq, kl_losses=None, annealing_factor=1.0):
-        out, probs, kl = _AttnFn.apply(self.flat, x, w, text_seq, self, float(annealing_factor), self.training)
+    def forward(self, x, w, text_seq, kl_losses=None, annealing_factor=1.0, text_len=None):
+        out, probs, kl = _AttnFn.apply(self.flat, x, w, text_seq, self, float(annealing_factor), self.training,
+                                       text_len)
         if kl_losses is not None:
             kl_losses.append(kl)
         return out, probs
@@ -594,18 +624,21 @@ class ConvolutionBlock(_EngineModule):
 
 class _GBFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, flat, x, w, text_seq, mod, anneal, train):
+    def forward(ctx, flat, x, w, text_seq, mod, anneal, train, text_len=None):
+        key_len = _key_len(text_len, x.shape[0], _seq_len(text_seq))
         eng = mod._engine()
         eng.prep()
         xh = _nhwc(x, mod._cdt)
         wf = w.float().contiguous()
+        if key_len is not None:
+            key_len = key_len.to(x.device)
         if mod.upsample:
             xh = ops.upsample2x(xh)  # nn.Upsample(2, bilinear, align_corners=False), :633, :657-658
         h, cbsv = _cb_fwd(eng, "b.conv_block.", xh, wf, mod.use_offset, mod.has_skip)
         eps = mod._eps("attn_block.moe.router.") if train else None
         eng._want_kl = True
-        out, probs, kl2, topi, asv = eng.attn_fwd("b.attn_block.", h, wf, _text_rows(text_seq), eps, anneal, train,
-                                                  save=train)
+        out, probs, kl2, topi, asv = eng.attn_fwd("b.attn_block.", h, wf, _text_rows(text_seq, text_len), eps, anneal,
+                                                  train, save=train, key_len=key_len)
         ctx.mod, ctx.cbsv, ctx.asv, ctx.kl2 = mod, cbsv, asv, kl2
         ctx.xshape, ctx.hshape, ctx.tshape = tuple(x.shape), h.shape, text_seq.shape
         kl = kl2[0].clone() if train else torch.zeros((), device=x.device)
@@ -623,7 +656,7 @@ class _GBFn(torch.autograd.Function):
         B = ctx.hshape[0]
         g_h = torch.empty(ctx.hshape, device=dev, dtype=mod._cdt)
         gw = torch.zeros(B, mod.latent_dim, device=dev)
-        g_ts = torch.zeros(B, ctx.asv["text_seq"].shape[1], device=dev)
+        g_ts = torch.zeros(ctx.asv["text_seq"].shape, device=dev)
         kl_coef = None if g_kl is None else (g_kl.float().reshape(1) * ctx.kl2[1:2]).contiguous()
         gp = None if g_probs is None else g_probs.float().contiguous()
         eng.attn_bwd("b.attn_block.", ctx.asv, _nhwc(g_out, mod._cdt), g_h, gw, g_ts, kl_coef=kl_coef, g_probs=gp)
@@ -635,12 +668,13 @@ class _GBFn(torch.autograd.Function):
             gprev = torch.empty(Bq, H2 // 2, W2 // 2, Cq, device=dev, dtype=mod._cdt)
             ops.upsample2x_bwd(g_in, gprev)
             g_in = gprev
-        return mod._grad_out(), g_in.permute(0, 3, 1, 2).float(), gw, g_ts.view(ctx.tshape), None, None, None
+        return mod._grad_out(), g_in.permute(0, 3, 1, 2).float(), gw, g_ts.view(ctx.tshape), None, None, None, None
 
 
 class GenerativeBlock(_EngineModule):
     """Reference :622-666: optional bilinear x2 upsample -> ConvolutionBlock -> AttentionBlock.
-    forward(x, w, text_seq, kl_losses=None, annealing_factor) -> (x, routing_probs)."""
+    forward(x, w, text_seq, kl_losses=None, annealing_factor, text_len=None) -> (x, routing_probs); ``text_seq``
+    [B, Lk, text_dim] and ``text_len`` as for AttentionBlock."""
     _IPRE = "b."
 
     def __init__(self, in_channels, out_channels, text_dim=768, upsample=False, resolution=None, num_experts=4,
@@ -657,8 +691,9 @@ class GenerativeBlock(_EngineModule):
         self.in_channels, self.out_channels, self.latent_dim = in_channels, out_channels, latent_dim
         self.upsample, self.use_offset, self.has_skip = upsample, offsets, in_channels != out_channels
 
-    def forward(self, x, w, text_seq, kl_losses=None, annealing_factor=1.0):
-        out, probs, kl = _GBFn.apply(self.flat, x, w, text_seq, self, float(annealing_factor), self.training)
+    def forward(self, x, w, text_seq, kl_losses=None, annealing_factor=1.0, text_len=None):
+        out, probs, kl = _GBFn.apply(self.flat, x, w, text_seq, self, float(annealing_factor), self.training,
+                                     text_len)
         if kl_losses is not None:
             kl_losses.append(kl)
         return out, probs

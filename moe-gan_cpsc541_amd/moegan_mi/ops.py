@@ -740,6 +740,30 @@ def attn_bwd(qkv, out, gout, lse, B, L, C, heads=8):
     return gqkv
 
 
+def xattn_fwd(q, kv, B, Lq, Lk, C, key_len=None, heads=8, *, out=None, lse=None):
+    """Text cross-attention (mg_xattn_fwd): q [B*Lq, C] (a column slice of a wider buffer is fine), kv [B*Lk, 2C]
+    (k | v); ``key_len`` int32 [B] on the device masks keys j >= key_len[b].  Returns (out [B*Lq, C], lse)."""
+    if out is None:
+        out = torch.empty(B * Lq, C, device=q.device, dtype=q.dtype)
+    if lse is None:
+        lse = torch.empty(B, heads, Lq, device=q.device, dtype=torch.float32)
+    call("mg_xattn_fwd", dt(q), ptr(q), q.stride(0), ptr(kv), kv.stride(0), ptr(key_len), B, Lq, Lk, C, heads,
+         ptr(out), ptr(lse), S())
+    return out, lse
+
+
+def xattn_bwd(q, kv, out, gout, lse, B, Lq, Lk, C, key_len=None, heads=8, *, gq=None, gkv=None):
+    """Backward of xattn_fwd (mg_xattn_bwd): (gq [B*Lq, C], gkv [B*Lk, 2C]); masked key rows of gkv are zero.
+    No atomics: the same inputs give the same bits."""
+    if gq is None:
+        gq = torch.empty(B * Lq, C, device=q.device, dtype=q.dtype)
+    if gkv is None:
+        gkv = torch.empty(B * Lk, 2 * C, device=q.device, dtype=q.dtype)
+    call("mg_xattn_bwd", dt(q), dt(gout), ptr(q), q.stride(0), ptr(kv), kv.stride(0), ptr(key_len), ptr(out),
+         ptr(gout), ptr(lse), B, Lq, Lk, C, heads, ptr(gq), ptr(gkv), S())
+    return gq, gkv
+
+
 # ---------------------------------------------------------------------------
 # router / MoE
 # ---------------------------------------------------------------------------

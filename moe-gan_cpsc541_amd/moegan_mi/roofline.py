@@ -27,7 +27,7 @@ FAMILIES = {
     "conv_wgrad+fold": ("mfma", ("mg_conv2d_wgrad",)),
     "expert_gemm": ("mfma", ("mg_gemm_grouped", "mg_gemm_grouped_wgrad", "mg_moe_ffn_fwd", "mg_moe_ffn_bwd")),
     "gemm": ("mfma", ("mg_gemm", "mg_gemm_batch")),
-    "attention": ("mfma", ("mg_attn_fwd", "mg_attn_bwd")),
+    "attention": ("mfma", ("mg_attn_fwd", "mg_attn_bwd", "mg_xattn_fwd", "mg_xattn_bwd")),
     "router_fwd": ("hbm", ("mg_router_fwd",)),
     "dispatch_combine": ("hbm", ("mg_gather_rows", "mg_moe_combine")),
     "warp_fwd": ("hbm", ("mg_warp_fwd", "mg_warp_fwd_scaled")),
@@ -73,7 +73,7 @@ KERNELS = [
     (r"gemm_kernel<.*LdMCConv", "conv_wgrad+fold"),
     (r"gemm_kernel<.*LdKCConv", "conv_fwd"),
     (r"gemm_kernel<|gemm_batch_kernel<|splitk_reduce_kernel", "gemm"),
-    (r"k_attn_", "attention"),
+    (r"k_attn_|k_xattn_", "attention"),
     (r"k_router_fwd", "router_fwd"),
     (r"k_gather_rows|k_combine", "dispatch_combine"),
     (r"k_warp_fwd", "warp_fwd"),
@@ -134,6 +134,10 @@ def work(name, a):
         return 4.0 * a["B"] * a["L"] * a["L"] * a["C"]
     if name == "mg_attn_bwd":  # dV, dP, dQ, dK (the S recompute is not algorithmic work)
         return 8.0 * a["B"] * a["L"] * a["L"] * a["C"]
+    if name == "mg_xattn_fwd":  # text cross-attention: S = Q K^T, O = P V over Lk keys
+        return 4.0 * a["B"] * a["Lq"] * a["Lk"] * a["C"]
+    if name == "mg_xattn_bwd":  # dV, dP, dQ, dK
+        return 8.0 * a["B"] * a["Lq"] * a["Lk"] * a["C"]
     if name == "mg_router_fwd":
         T, C, E, k = a["T"], a["C"], a["E"], a["k"]
         return T * C * ELT[a["dtype"]] + E * C * 4 + T * E * 8 + T * k * 8
@@ -344,6 +348,13 @@ def alg_bytes(name, a):
         return a["total_rows"] * (2 * a["C"] + 2 * a["Hd"]) * 2
     if name == "mg_moe_ffn_fwd":
         return a["total_rows"] * 2 * a["C"] * 2
+    if name == "mg_xattn_fwd":  # q, kv in; out, lse out
+        e = ELT[a["dtype"]]
+        return a["B"] * ((2 * a["Lq"] + 2 * a["Lk"]) * a["C"] * e + a["heads"] * a["Lq"] * 4)
+    if name == "mg_xattn_bwd":  # q, kv, out, gout, lse in; gq, gkv out
+        e = ELT[a["dtype"]]
+        return a["B"] * ((3 * a["Lq"] + 4 * a["Lk"]) * a["C"] * e + a["Lq"] * a["C"] * ELT[a["gout_dtype"]] +
+                         a["heads"] * a["Lq"] * 4)
     return None
 
 

@@ -42,6 +42,7 @@ from moegan_mi.params import ParamStore  # noqa: E402
 from moegan_mi.prefetch import DevicePrefetcher  # noqa: E402
 from moegan_mi.step import StepConfig, TrainStep  # noqa: E402
 from moegan_mi.checkpoint import load_resume, save_resume  # noqa: E402,F401
+from moegan_mi.modules import _key_len  # noqa: E402
 from moegan_mi.modules import (AttentionBlock, BayesianRouter, ConvolutionBlock, GenerativeBlock,  # noqa: E402,F401
                                ModulatedConv, ModulatedTransformationModule, SparseExpertFFN, SparseMoE,
                                create_optimizer_for_active_blocks)
@@ -130,12 +131,15 @@ class _FlatModule(nn.Module):
 
 class _GenFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, flat, z, text, mod, anneal, psi, train, want8, eps):
+    def forward(ctx, flat, z, text, mod, anneal, psi, train, want8, eps, tokens=None, key_len=None):
         eng = mod._engine()
         eng.prep()
-        need = any(ctx.needs_input_grad[:3])
+        need = any(ctx.needs_input_grad[:3]) or ctx.needs_input_grad[9]
+        if tokens is not None:
+            tokens = tokens.float().contiguous()
         img16, img8, kl2s, probs, _, gctx = eng.forward(z.float().contiguous(), text.float().contiguous(), eps,
-                                                        anneal, psi, train=train, save=need, want_img8=want8)
+                                                        anneal, psi, train=train, save=need, want_img8=want8,
+                                                        text_tokens=tokens, text_len=key_len)
         out16 = img16[..., :3].permute(0, 3, 1, 2).float().contiguous()
         out8 = img8[..., :3].permute(0, 3, 1, 2).float().contiguous() if img8 is not None else z.new_zeros(0)
         if train:
@@ -166,8 +170,10 @@ class _GenFn(torch.autograd.Function):
         if ctx.kl2 is not None and gkl is not None:
             kl_coef = (gkl.float() * ctx.kl2[:, 1]).contiguous()
         gp = [None if g is None else g.float().contiguous() for g in gprobs]
-        gz, gtext = eng.backward(ctx.gctx, gi16, kl_coef=kl_coef, want_input_grads=True, g_probs=gp, g_img8=gi8)
-        return st.grad.clone(), gz, gtext, None, None, None, None, None, None
+        gin = eng.backward(ctx.gctx, gi16, kl_coef=kl_coef, want_input_grads=True, g_probs=gp, g_img8=gi8)
+        gz, gtext = gin[0], gin[1]
+        gtok = gin[2] if len(gin) > 2 else None  # the token gradient after a forward with text_tokens
+        return st.grad.clone(), gz, gtext, None, None, None, None, None, None, gtok, None
 
 
 class AuroraGenerator(_FlatModule):
@@ -210,7 +216,13 @@ class AuroraGenerator(_FlatModule):
         return text_or_embeddings
 
     def forward(self, z, text_input, truncation_psi=0.7, return_routing=False, return_intermediate=False,
-                annealing_factor=1.0):
+                annealing_factor=1.0, text_tokens=None, text_len=None):
+        """``text_tokens`` [B, Lk, 512] (1 <= Lk <= 128; per-token text features, e.g. CLIP's token sequence
+        projected to 512): the attention blocks cross-attend over text_projection applied per token instead of the
+        one pooled row; ``text_len`` (list or int tensor [B], 1 <= len <= Lk) masks each image's padding tokens.
+        The pooled ``text_input`` still feeds the mapping network.  Defaults: the reference's one-token path.
+        Training with tokens goes through this autograd path (the fused TrainStep and the reference dataset layout
+        carry pooled embeddings only)."""
         self._require_gpu()
         text = self.encode_text(text_input)
         B = z.shape[0]
@@ -221,8 +233,17 @@ class AuroraGenerator(_FlatModule):
                 raise ValueError(f"Batch size mismatch: z has batch size {B}, but text_embeddings has batch size "
                                  f"{text.shape[0]}")
         eps = _eps_for(self._store) if self.training else None
+        key_len = None
+        if text_tokens is not None:
+            if text_tokens.dim() != 3 or text_tokens.shape[0] != B or text_tokens.shape[2] != text.shape[1]:
+                raise ValueError(f"text_tokens: [{B}, Lk, {text.shape[1]}], got {tuple(text_tokens.shape)}")
+            if not 1 <= text_tokens.shape[1] <= 128:
+                raise ValueError("text_tokens: 1 to 128 tokens")
+            key_len = _key_len(text_len, B, text_tokens.shape[1], z.device)
+        elif text_len is not None:
+            raise ValueError("text_len needs text_tokens")
         outs = _GenFn.apply(self.flat, z, text, self, float(annealing_factor), float(truncation_psi), self.training,
-                            bool(return_intermediate), eps)
+                            bool(return_intermediate), eps, text_tokens, key_len)
         img16, img8, kl = outs[0], outs[1], outs[2]
         probs = list(outs[3:])
         if return_routing and return_intermediate:
@@ -662,8 +683,10 @@ def _validate(generator, discriminator, loader, gan_loss, temperature_factor, ef
     return vm
 
 
-def sample_aurora_gan(generator, text_prompt, num_samples=1, truncation_psi=0.7, device=DEVICE):
-    """Reference :1672-1709: eval mode (hard top-1 routing), clamp to [-1, 1]."""
+def sample_aurora_gan(generator, text_prompt, num_samples=1, truncation_psi=0.7, device=DEVICE, text_tokens=None,
+                      text_len=None):
+    """Reference :1672-1709: eval mode (hard top-1 routing), clamp to [-1, 1].  ``text_tokens`` [B or 1, Lk, 512] /
+    ``text_len``: per-token text features for the cross-attention (AuroraGenerator.forward)."""
     generator.eval()
     z = torch.randn(num_samples, LATENT_DIM, device=device, dtype=torch.float32)
     if isinstance(text_prompt, str) or (isinstance(text_prompt, list) and isinstance(text_prompt[0], str)):
@@ -671,6 +694,13 @@ def sample_aurora_gan(generator, text_prompt, num_samples=1, truncation_psi=0.7,
     text_prompt = text_prompt.float().to(device)
     if num_samples > 1 and text_prompt.size(0) == 1:
         text_prompt = text_prompt.repeat(num_samples, 1)
+    if text_tokens is not None:
+        text_tokens = text_tokens.float().to(device)
+        if num_samples > 1 and text_tokens.size(0) == 1:
+            text_tokens = text_tokens.repeat(num_samples, 1, 1)
+            if text_len is not None:
+                text_len = torch.as_tensor(text_len).reshape(-1).repeat(num_samples)
     with torch.no_grad():
-        fake, _ = generator(z, text_prompt, truncation_psi=truncation_psi)
+        fake, _ = generator(z, text_prompt, truncation_psi=truncation_psi, text_tokens=text_tokens,
+                            text_len=text_len)
         return torch.clamp(fake, -1, 1)
