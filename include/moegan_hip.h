@@ -266,6 +266,9 @@ int mg_attn_fwd(int dtype, const void* qkv, int B, int L, int C, int heads, void
 /* Self-attention backward -> gqkv [B*L, 3C]. */
 int mg_attn_bwd(int dtype, int gout_dtype, const void* qkv, const void* out, const void* gout, const float* lse, int B, int L, int C, int heads, void* gqkv, void* stream);
 
+/* Ragged causal self-attention forward (CLIP text tower): qkv [R, 3C] (q | k | v), sequence b = rows row_off[b] .. row_off[b+1]-1 (row_off device int32 [B+1], 1 <= length <= Lmax <= 128), query i attends to keys j <= i of its sequence; out [R, C]. bf16 with head dim 64 runs on MFMA, fp32 and other head dims (16 / 32) on a scalar kernel; no atomics, bit-reproducible. */
+int mg_attn_causal_fwd(int dtype, const void* qkv, const int32_t* row_off, int B, int Lmax, int C, int heads, void* out, void* stream);
+
 /* Text cross-attention core (8 heads) for a multi-token text sequence: q [B*Lq, C] (pitch ldq), kv [B*Lk, 2C] (k | v, pitch ldkv), out [B*Lq, C], lse [B, heads, Lq]; key_len (device int32 [B] or NULL): keys j >= key_len[b] are masked. Lk <= 128, Lq <= 1024. t2i_moe_gan.py:549-556. */
 int mg_xattn_fwd(int dtype, const void* q, int64_t ldq, const void* kv, int64_t ldkv, const int32_t* key_len, int B, int Lq, int Lk, int C, int heads, void* out, float* lse, void* stream);
 

@@ -740,6 +740,16 @@ def attn_bwd(qkv, out, gout, lse, B, L, C, heads=8):
     return gqkv
 
 
+def attn_causal_fwd(qkv, row_off, B, Lmax, C, heads=8, *, out=None):
+    """Ragged causal self-attention (mg_attn_causal_fwd): qkv [R, 3C] holds B sequences back to back, sequence b =
+    rows row_off[b] .. row_off[b+1]-1 (``row_off`` int32 [B+1] on the device, every length in 1..Lmax, Lmax <= 128);
+    query i attends to keys j <= i of its own sequence.  Returns out [R, C]."""
+    if out is None:
+        out = torch.empty(qkv.shape[0], C, device=qkv.device, dtype=qkv.dtype)
+    call("mg_attn_causal_fwd", dt(qkv), ptr(qkv), ptr(row_off), B, Lmax, C, heads, ptr(out), S())
+    return out
+
+
 def xattn_fwd(q, kv, B, Lq, Lk, C, key_len=None, heads=8, *, out=None, lse=None):
     """Text cross-attention (mg_xattn_fwd): q [B*Lq, C] (a column slice of a wider buffer is fine), kv [B*Lk, 2C]
     (k | v); ``key_len`` int32 [B] on the device masks keys j >= key_len[b].  Returns (out [B*Lq, C], lse)."""

@@ -65,11 +65,37 @@ def set_clip_model(model):
     _clip_model = model
 
 
-def load_clip_weights(path, device=None):
+def load_clip_weights(path, device=None, bpe_path=None):
     """Register the forward-only CLIP image tower (moegan_mi/clip_vit.py) built from a local OpenAI CLIP
-    state_dict / safetensors file; the CLIP loss terms (:66-119) then use it.  Returns the encoder."""
+    state_dict / safetensors file; the CLIP loss terms (:66-119) then use it.  Returns the encoder.
+
+    When the file also holds the text side (``token_embedding.weight`` ...), the registered object is a
+    moegan_mi.clip_text.ClipModel: the same ``encode_image`` / ``encode_generated`` plus ``encode_text`` (token ids,
+    or strings when ``bpe_path`` names CLIP's merges file, which also gives it ``tokenize``).  A file with only
+    ``visual.*`` keys registers the image tower alone, as before."""
     from moegan_mi.clip_vit import ClipImageEncoder
-    enc = ClipImageEncoder.from_file(path, device=device or DEVICE)
+    if str(path).endswith(".safetensors"):
+        from safetensors.torch import load_file
+        sd = load_file(str(path))
+    else:
+        sd = torch.load(path, map_location="cpu", weights_only=True)
+    from moegan_mi.clip_text import ClipModel, ClipTextEncoder, has_text_tower
+    has_image = any(k.startswith("visual.") for k in sd) or "conv1.weight" in sd
+    image = ClipImageEncoder(sd, device=device or DEVICE) if has_image else None
+    if not has_text_tower(sd):
+        if bpe_path is not None:
+            raise ValueError("load_clip_weights: bpe_path given but the file holds no text-tower weights")
+        enc = image if image is not None else ClipImageEncoder(sd, device=device or DEVICE)
+    else:
+        tok = None
+        if bpe_path is not None:
+            from moegan_mi.clip_bpe import ClipTokenizer
+            tok = ClipTokenizer(bpe_path)
+        text = ClipTextEncoder(sd, device=device or DEVICE)
+        if tok is not None and tok.vocab_size != text.vocab_size:
+            raise ValueError(f"load_clip_weights: the merges file gives {tok.vocab_size} tokens, the weights "
+                             f"{text.vocab_size}")
+        enc = ClipModel(text, image, tok)
     set_clip_model(enc)
     return enc
 
@@ -298,9 +324,26 @@ def encode_text_with_clip(text, model=None):
     model = model or get_clip_model()[0]
     if isinstance(text, str):
         text = [text]
+    if hasattr(model, "tokenize"):  # the project's own text tower with its tokenizer (load_clip_weights(bpe_path=))
+        with torch.no_grad():
+            return model.encode_text(model.tokenize(text)).float()
     import clip  # a locally provided CLIP package
     with torch.no_grad():
         return model.encode_text(clip.tokenize(text).to(DEVICE)).float()
+
+
+def encode_prompt(text, model=None):
+    """Prompt(s) -> (pooled [N, 512], tokens [N, Lk, 512], text_len int32 [N]) on the registered text tower
+    (moegan_mi/clip_text.py): the pooled row feeds the mapping network, ``tokens`` / ``text_len`` are
+    AuroraGenerator.forward's ``text_tokens=`` / ``text_len=``."""
+    model = model or get_clip_model()[0]
+    if not hasattr(model, "tokenize"):
+        raise RuntimeError("encode_prompt needs the text tower and its tokenizer: load_clip_weights(path, bpe_path=...)")
+    if isinstance(text, str):
+        text = [text]
+    with torch.no_grad():
+        pooled, tokens, text_len = model.encode_text(model.tokenize(text), return_tokens=True)
+    return pooled.float(), tokens.float(), text_len
 
 
 class CLIPLoss(nn.Module):
@@ -684,13 +727,17 @@ def _validate(generator, discriminator, loader, gan_loss, temperature_factor, ef
 
 
 def sample_aurora_gan(generator, text_prompt, num_samples=1, truncation_psi=0.7, device=DEVICE, text_tokens=None,
-                      text_len=None):
+                      text_len=None, prompt_tokens=False):
     """Reference :1672-1709: eval mode (hard top-1 routing), clamp to [-1, 1].  ``text_tokens`` [B or 1, Lk, 512] /
-    ``text_len``: per-token text features for the cross-attention (AuroraGenerator.forward)."""
+    ``text_len``: per-token text features for the cross-attention (AuroraGenerator.forward).  ``prompt_tokens``
+    with a string prompt: the prompt's own token features (encode_prompt) feed the cross-attention too."""
     generator.eval()
     z = torch.randn(num_samples, LATENT_DIM, device=device, dtype=torch.float32)
     if isinstance(text_prompt, str) or (isinstance(text_prompt, list) and isinstance(text_prompt[0], str)):
-        text_prompt = encode_text_with_clip(text_prompt)
+        if prompt_tokens and text_tokens is None:
+            text_prompt, text_tokens, text_len = encode_prompt(text_prompt)
+        else:
+            text_prompt = encode_text_with_clip(text_prompt)
     text_prompt = text_prompt.float().to(device)
     if num_samples > 1 and text_prompt.size(0) == 1:
         text_prompt = text_prompt.repeat(num_samples, 1)
