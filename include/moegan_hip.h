@@ -275,6 +275,12 @@ int mg_xattn_fwd(int dtype, const void* q, int64_t ldq, const void* kv, int64_t 
 /* Text cross-attention backward -> gq [B*Lq, C], gkv [B*Lk, 2C] (written, masked key rows exactly 0); no atomics, bit-reproducible. */
 int mg_xattn_bwd(int dtype, int gout_dtype, const void* q, int64_t ldq, const void* kv, int64_t ldkv, const int32_t* key_len, const void* out, const void* gout, const float* lse, int B, int Lq, int Lk, int C, int heads, void* gq, void* gkv, void* stream);
 
+/* Text cross-attention over packed key rows: kv [rows, 2C] holds the images' live keys back to back, image b = rows row_off[b] .. row_off[b+1]-1 (row_off device int32 [B+1], 1 <= length <= Lmax, Lmax a multiple of 32 and <= 128, row_off[B] <= rows); q / out / lse as mg_xattn_fwd. Nothing past a span is read. */
+int mg_xattn_ragged_fwd(int dtype, const void* q, int64_t ldq, const void* kv, int64_t ldkv, const int32_t* row_off, int B, int Lq, int Lmax, int rows, int C, int heads, void* out, float* lse, void* stream);
+
+/* Backward of mg_xattn_ragged_fwd -> gq [B*Lq, C], gkv [rows, 2C]: every row below `rows` is written, the pad rows row_off[B] .. rows-1 as exact zeros; no atomics, bit-reproducible. */
+int mg_xattn_ragged_bwd(int dtype, int gout_dtype, const void* q, int64_t ldq, const void* kv, int64_t ldkv, const int32_t* row_off, const void* out, const void* gout, const float* lse, int B, int Lq, int Lmax, int rows, int C, int heads, void* gq, void* gkv, void* stream);
+
 /* Head text-branch backward: g_tpre, dW2 text rows (all taps). */
 int mg_d_text_bwd(const float* g_tb, const float* t, const float* w2sum, int B, int Ct, int cofs, float* g_tpre, float* dW2, void* stream);
 

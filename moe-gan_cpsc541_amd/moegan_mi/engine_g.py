@@ -626,11 +626,13 @@ class GeneratorEngine:
     # ------------------------------------------------------------------
     # AttentionBlock  (t2i_moe_gan.py:493-576)
     # ------------------------------------------------------------------
-    def attn_fwd(self, pre, x, w, text_seq, eps, anneal, train=True, save=True, kl_out=None, key_len=None):
+    def attn_fwd(self, pre, x, w, text_seq, eps, anneal, train=True, save=True, kl_out=None, key_len=None,
+                 rag=None):
         """``text_seq`` [B, 512]: the one-token sequence (cross-attention collapsed algebraically); [B, Lk, 512]
-        (with an optional ``key_len`` int32 [B] padding mask): the multi-token branch (_attn_fwd_seq)."""
-        if text_seq.dim() == 3:
-            return self._attn_fwd_seq(pre, x, w, text_seq, eps, anneal, train, save, kl_out, key_len)
+        (with an optional ``key_len`` int32 [B] padding mask): the multi-token branch (_attn_fwd_seq); ``rag`` =
+        (row_off int32 [B+1], lk_max): the same branch over packed rows ``text_seq`` [rows, 512]."""
+        if text_seq.dim() == 3 or rag is not None:
+            return self._attn_fwd_seq(pre, x, w, text_seq, eps, anneal, train, save, kl_out, key_len, rag)
         B, H, W, C = x.shape
         L_ = H * W
         T = B * L_
@@ -710,8 +712,9 @@ class GeneratorEngine:
     # ------------------------------------------------------------------
     # AttentionBlock with a multi-token text sequence [B, Lk, 512] (t2i_moe_gan.py:525-555 as written: the
     # softmax over Lk keys is real, so norm2 and the q / k rows of cross_attn.in_proj are live).  Used by the
-    # module API and the generator's autograd path; the fused training step feeds one pooled token and never
-    # comes here.
+    # module API and the generator's autograd path with padded tokens, and by the fused training step with packed
+    # rows (``rag``: the text side runs over the batch's live rows, padded to the row bucket, and the ragged
+    # cross-attention kernels read image b's keys at row_off[b] .. row_off[b+1]).
     # ------------------------------------------------------------------
     def _xattn_kv(self, pre, rows, C):
         """tp = text_proj(text rows) [B*Lk, C] (fp32) and its packed key | value projections kv [B*Lk, 2C] in the
@@ -731,12 +734,12 @@ class GeneratorEngine:
             chain[p] = dict(tp=tp, kv=kv)
         return chain
 
-    def _attn_fwd_seq(self, pre, x, w, text_seq, eps, anneal, train, save, kl_out, key_len):
+    def _attn_fwd_seq(self, pre, x, w, text_seq, eps, anneal, train, save, kl_out, key_len, rag=None):
         B, H, W, C = x.shape
         L_ = H * W
         T = B * L_
-        Lk = text_seq.shape[1]
-        rows = text_seq.reshape(B * Lk, text_seq.shape[2])
+        Lk = text_seq.shape[1] if rag is None else rag[1]
+        rows = text_seq.reshape(-1, text_seq.shape[-1])
         xf0, sv_in = self.mc_fwd(pre + "proj_in.", x, w, save=save)
         xf0 = xf0.view(T, C)
         n1, mu1, rs1 = ops.layernorm_fwd(xf0, self.P(pre + "norm1.weight"), self.P(pre + "norm1.bias"))
@@ -752,7 +755,10 @@ class GeneratorEngine:
         n2, mu2, rs2 = ops.layernorm_fwd(xf_s, self.P(pre + "norm2.weight"), self.P(pre + "norm2.bias"))
         q = ops.linear(n2, self.Pc(pre + "cross_attn.in_proj_weight")[:C],
                        bias=self.P(pre + "cross_attn.in_proj_bias")[:C])
-        o, lse2 = ops.xattn_fwd(q, kv, B, L_, Lk, C, key_len=key_len)
+        if rag is None:
+            o, lse2 = ops.xattn_fwd(q, kv, B, L_, Lk, C, key_len=key_len)
+        else:
+            o, lse2 = ops.xattn_ragged_fwd(q, kv, rag[0], B, L_, Lk, C)
         xf1 = ops.linear(o, self.Pc(pre + "cross_attn.out_proj.weight"), bias=self.P(pre + "cross_attn.out_proj.bias"),
                          resid=xf_s, ld_res=C)
         n3, mu3, rs3 = ops.layernorm_fwd(xf1, self.P(pre + "norm3.weight"), self.P(pre + "norm3.bias"))
@@ -770,6 +776,7 @@ class GeneratorEngine:
         if save:
             sv = dict(sv_in=sv_in, xf0=xf0, n1=n1, mu1=mu1, rs1=rs1, qkv=qkv, att=att, lse=lse, tp=tp, kv=kv,
                       xf_s=xf_s, n2=n2, mu2=mu2, rs2=rs2, q=q, o=o, lse2=lse2, key_len=key_len, rows=rows, Lk=Lk,
+                      rag=rag,
                       xf1=xf1, n3=n3, mu3=mu3, rs3=rs3, sv_moe=sv_moe, sv_out=sv_out, text_seq=text_seq, B=B, L=L_)
         return out, probs, kl2, topi, sv
 
@@ -787,7 +794,12 @@ class GeneratorEngine:
         g_o = ops.linear_dgrad(g_xf1, self.Pc(pre + "cross_attn.out_proj.weight"))
         ops.linear_wgrad(g_xf1, sv["o"], self.G(pre + "cross_attn.out_proj.weight"))
         ops.colsum(g_xf1, self.G(pre + "cross_attn.out_proj.bias"))  # (at once: g_xf1 is accumulated into below)
-        g_q, g_kv = ops.xattn_bwd(sv["q"], sv["kv"], sv["o"], g_o, sv["lse2"], B, L_, Lk, C, key_len=sv["key_len"])
+        if sv["rag"] is None:
+            g_q, g_kv = ops.xattn_bwd(sv["q"], sv["kv"], sv["o"], g_o, sv["lse2"], B, L_, Lk, C,
+                                      key_len=sv["key_len"])
+        else:  # (the bucket's pad rows of g_kv come back as zeros: the sums over the rows below see nothing of them)
+            g_q, g_kv = ops.xattn_ragged_bwd(sv["q"], sv["kv"], sv["rag"][0], sv["o"], g_o, sv["lse2"], B, L_, Lk,
+                                             C)
         gWi, gbi = self.G(pre + "cross_attn.in_proj_weight"), self.G(pre + "cross_attn.in_proj_bias")
         g_n2 = ops.linear_dgrad(g_q, self.Pc(pre + "cross_attn.in_proj_weight")[:C])
         ops.linear_wgrad(g_q, sv["n2"], gWi[:C])
@@ -795,14 +807,15 @@ class GeneratorEngine:
         g_xfs = g_xf1  # residual path, accumulate LN2 backward into it
         ops.layernorm_bwd(g_n2, sv["xf_s"], sv["mu2"], sv["rs2"], self.P(pre + "norm2.weight"), g_xfs,
                           self.G(pre + "norm2.weight"), self.G(pre + "norm2.bias"), accumulate=1)
-        # key / value side: B * Lk text rows, fp32 like the other per-image chains
+        # key / value side: B * Lk text rows (packed: the row bucket), fp32 like the other per-image chains
         g_kv32 = g_kv if g_kv.dtype == torch.float32 else ops.cast(g_kv, torch.float32)
         ops.linear_wgrad(g_kv32, sv["tp"], gWi[C:])
         ops.colsum(g_kv32, gbi[C:])
         g_tp = ops.linear_dgrad(g_kv32, self.P(pre + "cross_attn.in_proj_weight")[C:])
         ops.linear_wgrad(g_tp, sv["rows"], self.G(pre + "text_proj.weight"))
         ops.colsum(g_tp, self.G(pre + "text_proj.bias"))
-        ops.linear_dgrad(g_tp, self.P(pre + "text_proj.weight"), out=g_text_seq.view(B * Lk, -1), accumulate=1)
+        ops.linear_dgrad(g_tp, self.P(pre + "text_proj.weight"), out=g_text_seq.view(sv["rows"].shape[0], -1),
+                         accumulate=1)
         # self-attention
         g_att = ops.linear_dgrad(g_xfs, self.Pc(pre + "self_attn.out_proj.weight"))
         ops.linear_wgrad(g_xfs, sv["att"], self.G(pre + "self_attn.out_proj.weight"))
@@ -830,21 +843,32 @@ class GeneratorEngine:
             hs.append(h)
         return h, hs
 
-    def _prefix_fwd(self, z, text, psi, save, text_tokens=None, text_len=None):
+    def _prefix_fwd(self, z, text, psi, save, text_tokens=None, text_len=None, text_rows=None, row_off=None,
+                    lk_max=None):
         """The part of the forward that does not depend on the router samples: text projection, mapping,
         truncation, every style / demodulation, the constant and gen_block_4's convolution block.  Given the
         same z, text and weights it is identical in the D-phase and G-phase forwards of one step
         (t2i_moe_gan.py:1288-1296 and :1351-1357 feed the same z; G is not updated in between).
         ``text_tokens`` [B, Lk, 512] (with an optional ``text_len`` int32 [B]): the text sequence the attention
         blocks attend over is text_projection applied per token instead of the one projected pooled row (:790);
-        the pooled ``text`` still feeds the mapping network."""
+        the pooled ``text`` still feeds the mapping network.  ``text_rows`` [rows, 512] / ``row_off`` int32 [B+1] /
+        ``lk_max``: the same with the live token rows packed back to back (moegan_mi.tokens.pack_tokens); the
+        projection runs over ``rows`` rows (the bucket's zero pad rows come out as bias-only rows nothing reads)."""
         B = z.shape[0]
         dev = self.dev
         if text.shape[0] != B and text.shape[0] == 1:
             text = text.expand(B, -1).contiguous()
         # text projection (:682-687, :790)
+        rag = None
+        if text_rows is not None:
+            assert text_tokens is None and text_len is None, "text_rows and text_tokens are mutually exclusive"
+            assert row_off is not None and lk_max is not None, "packed text rows need row_off and lk_max"
+            assert text_rows.dim() == 2 and text_rows.shape[0] >= B and row_off.numel() == B + 1
+            assert row_off.dtype == torch.int32 and row_off.device == text_rows.device
+            rag = (row_off, int(lk_max))
         Lk = None if text_tokens is None else text_tokens.shape[1]
-        text_c = self._p(text if Lk is None else text_tokens.reshape(B * Lk, -1))  # (B * Lk rows with tokens)
+        text_c = self._p(text_rows if rag is not None else
+                         text if Lk is None else text_tokens.reshape(B * Lk, -1))  # (B * Lk rows with tokens)
         t0 = ops.linear(text_c, self.Pp("text_projection.0.weight"), bias=self.P("text_projection.0.bias"),
                         out_dtype=torch.float32)
         t1, tmu, trs = ops.layernorm_fwd(t0, self.P("text_projection.1.weight"), self.P("text_projection.1.bias"),
@@ -889,17 +913,21 @@ class GeneratorEngine:
         name0, _, _, _, up0, _ = self.blocks[0]
         assert not up0
         x0, cbsv0 = self.cb_fwd(name0 + ".conv_block.", x, w, save=save)
-        if Lk is not None:
+        if rag is not None:
+            xchain = self._xattn_seq_chain(text_seq)  # (text_seq stays [rows, 512])
+        elif Lk is not None:
             text_seq = text_seq.view(B, Lk, -1)
             xchain = self._xattn_seq_chain(text_seq)
         else:
             xchain = self._xattn_chain(text_seq) if self.attn_blocks else {}
-        return dict(B=B, Lk=Lk, text_len=text_len, text=text, text_c=text_c, t0=t0, t1=t1, t1c=t1c, tmu=tmu, trs=trs, text_seq=text_seq,
+        return dict(B=B, Lk=Lk, rag=rag, text_len=text_len, text=text, text_c=text_c, t0=t0, t1=t1, t1c=t1c, tmu=tmu,
+                    trs=trs, text_seq=text_seq,
                     hs=hs, h3=h3, w=w, w_c=w_c, psi=psi, S=S, S2=S2, D=D, x0=x0, cbsv0=cbsv0, save=save,
                     xchain=xchain)
 
     def forward(self, z, text, eps, anneal=1.0, psi=0.7, train=True, save=True, want_img8=False, want_kl=True,
-                keep_prefix=False, prefix=None, text_tokens=None, text_len=None):
+                keep_prefix=False, prefix=None, text_tokens=None, text_len=None, text_rows=None, row_off=None,
+                lk_max=None):
         """Returns (img [B,R,R,8] padded NHWC, the intermediate R/2 image or None, kl2 list, probs list, ctx);
         R = max_res (16: the reference generator, img16 / img8).  kl2 / probs / eps: one per attention block.
         ``want_kl=False`` skips the routers' KL terms (their kl2 entries are None).
@@ -907,11 +935,14 @@ class GeneratorEngine:
         activations and returns it as ``self.last_prefix``; ``prefix=`` reuses such a prefix (same z, text,
         psi and weights) instead of recomputing it.
         ``text_tokens`` [B, Lk, 512] / ``text_len`` int32 [B]: per-token text features for the attention blocks'
-        cross-attention (keys j >= text_len[b] masked); training with them goes through the modules' autograd
-        path (the fused step and the reference dataset carry pooled embeddings only)."""
+        cross-attention (keys j >= text_len[b] masked), the form of the modules' autograd path.
+        ``text_rows`` [rows, 512] (pad rows zero) / ``row_off`` device int32 [B+1] / ``lk_max``: the same features
+        with the live rows packed back to back (tokens.pack_tokens), the form the fused step trains on; not
+        together with ``text_tokens``."""
         self._want_kl = want_kl
         if prefix is None:
-            prefix = self._prefix_fwd(z, text, psi, save or keep_prefix, text_tokens, text_len)
+            prefix = self._prefix_fwd(z, text, psi, save or keep_prefix, text_tokens, text_len, text_rows, row_off,
+                                      lk_max)
         else:
             assert prefix["B"] == z.shape[0] and prefix["psi"] == psi and (prefix["save"] or not save)
             self._S, self._S2, self._D = prefix["S"], prefix["S2"], prefix["D"]
@@ -948,7 +979,7 @@ class GeneratorEngine:
                 x, p, kl2, topi, asv = self.attn_fwd(name + ".attn_block.", x, w, text_seq,
                                                      None if eps is None else eps[ai], anneal, train, save,
                                                      kl_out=None if klbuf is None else klbuf[ai],
-                                                     key_len=prefix["text_len"])
+                                                     key_len=prefix["text_len"], rag=prefix["rag"])
                 ai += 1
                 probs.append(p)
                 kl2s.append(kl2)
@@ -962,7 +993,7 @@ class GeneratorEngine:
         ctx = None
         if save:
             ctx = {k: prefix[k] for k in ("B", "text", "text_c", "t0", "t1", "t1c", "tmu", "trs", "text_seq", "hs",
-                                          "h3", "w", "w_c", "psi", "Lk")}
+                                          "h3", "w", "w_c", "psi", "Lk", "rag")}
             ctx.update(z=z, blocks=blocks, rgbsv=rgbsv, rgb8sv=rgb8sv)
         self.last_klbuf = klbuf  # kl2s are its rows (TrainStep reads the buffer instead of stacking them)
         return img16, img8, kl2s, probs, topis, ctx
@@ -971,12 +1002,15 @@ class GeneratorEngine:
         """Accumulate all generator parameter gradients for d loss / d img16 (+ balance coef on the last
         router, + KL coefficients [3] per router).  Optional: per-router d loss / d probs [T, E] (g_probs list)
         and d loss / d img8 (needs forward(..., want_img8=True, save=True)).  Returns (gz, gtext) if requested;
-        after a forward with ``text_tokens``, (gz, gtext, gtokens [B, Lk, 512])."""
+        after a forward with ``text_tokens``, (gz, gtext, gtokens [B, Lk, 512]); after one with ``text_rows``,
+        gtokens is packed [rows, 512] like them, its pad rows exactly 0."""
         B = ctx["B"]
         dev = self.dev
-        Lk = ctx["Lk"]  # None: pooled text only
+        Lk = ctx["Lk"]  # None: pooled text only (or packed rows: ctx["rag"])
+        rag = ctx["rag"]
         gw = ops.zeros(B, 512, device=dev)
-        g_ts = ops.zeros(B if Lk is None else B * Lk, 512, device=dev)
+        n_ts = ctx["text_seq"].shape[0] if rag is not None else B if Lk is None else B * Lk
+        g_ts = ops.zeros(n_ts, 512, device=dev)
         self._router_bwd, self._xattn_bwd = [], []
         self._defer = True  # per-block small GEMMs are batched over the blocks after the block loop
         if self.style_cols:
@@ -1066,10 +1100,12 @@ class GeneratorEngine:
         ops.linear_wgrad(self._p(g_t0), ctx["text_c"], self.G("text_projection.0.weight"))
         ops.colsum(g_t0, self.G("text_projection.0.bias"), defer=True)
         if not want_input_grads:
-            return (None, None) if Lk is None else (None, None, None)
+            return (None, None) if Lk is None and rag is None else (None, None, None)
         gtext = ops.linear_dgrad(g_t0, self.P("text_projection.0.weight"))
         zd = ctx["z"].shape[1]
         gz = g_zt[:, :zd].float().contiguous()
+        if rag is not None:
+            return gz, g_zt[:, zd:].float().contiguous(), gtext
         if Lk is not None:  # the projection saw the tokens; the pooled text reaches the mapping network only
             return gz, g_zt[:, zd:].float().contiguous(), gtext.view(B, Lk, -1)
         gtext = gtext + g_zt[:, zd:].float()

@@ -535,8 +535,8 @@ class AttentionBlock(_EngineModule):
     cross-attention kernels).  forward(x, w, text_seq, kl_losses=None, annealing_factor, text_len=None) ->
     (x_out, routing_probs); the router's KL is appended to ``kl_losses`` as in the reference.  ``text_len`` (list
     or int tensor [B], 1 <= len <= Lk) masks the keys past each image's length (key_padding_mask of a right-padded
-    token sequence; the reference passes none).  Training with token sequences goes through this autograd path:
-    the fused TrainStep feeds the pooled embedding only."""
+    token sequence; the reference passes none).  This autograd path takes the padded form; the fused TrainStep
+    takes the packed one (moegan_mi.tokens)."""
     _IPRE = "b.attn_block."
 
     def __init__(self, dim, text_dim=512, heads=8, num_experts=4, topk=None, latent_dim=LATENT_DIM, dtype="fp32",

@@ -774,6 +774,32 @@ def xattn_bwd(q, kv, out, gout, lse, B, Lq, Lk, C, key_len=None, heads=8, *, gq=
     return gq, gkv
 
 
+def xattn_ragged_fwd(q, kv, row_off, B, Lq, lmax, C, heads=8, *, out=None, lse=None):
+    """Text cross-attention over packed key rows (mg_xattn_ragged_fwd): kv [rows, 2C] holds the images' live keys
+    back to back, image b = rows row_off[b] .. row_off[b+1]-1 (``row_off`` int32 [B+1] on the device, every length in
+    1..lmax, lmax a multiple of 32, at most 128).  Returns (out [B*Lq, C], lse)."""
+    if out is None:
+        out = torch.empty(B * Lq, C, device=q.device, dtype=q.dtype)
+    if lse is None:
+        lse = torch.empty(B, heads, Lq, device=q.device, dtype=torch.float32)
+    call("mg_xattn_ragged_fwd", dt(q), ptr(q), q.stride(0), ptr(kv), kv.stride(0), ptr(row_off), B, Lq, lmax,
+         kv.shape[0], C, heads, ptr(out), ptr(lse), S())
+    return out, lse
+
+
+def xattn_ragged_bwd(q, kv, row_off, out, gout, lse, B, Lq, lmax, C, heads=8, *, gq=None, gkv=None):
+    """Backward of xattn_ragged_fwd (mg_xattn_ragged_bwd): (gq [B*Lq, C], gkv [rows, 2C]); the pad rows
+    row_off[B] .. rows-1 of gkv are zero.  No atomics: the same inputs give the same bits."""
+    rows = kv.shape[0]
+    if gq is None:
+        gq = torch.empty(B * Lq, C, device=q.device, dtype=q.dtype)
+    if gkv is None:
+        gkv = torch.empty(rows, 2 * C, device=q.device, dtype=q.dtype)
+    call("mg_xattn_ragged_bwd", dt(q), dt(gout), ptr(q), q.stride(0), ptr(kv), kv.stride(0), ptr(row_off), ptr(out),
+         ptr(gout), ptr(lse), B, Lq, lmax, rows, C, heads, ptr(gq), ptr(gkv), S())
+    return gq, gkv
+
+
 # ---------------------------------------------------------------------------
 # router / MoE
 # ---------------------------------------------------------------------------

@@ -27,7 +27,8 @@ FAMILIES = {
     "conv_wgrad+fold": ("mfma", ("mg_conv2d_wgrad",)),
     "expert_gemm": ("mfma", ("mg_gemm_grouped", "mg_gemm_grouped_wgrad", "mg_moe_ffn_fwd", "mg_moe_ffn_bwd")),
     "gemm": ("mfma", ("mg_gemm", "mg_gemm_batch")),
-    "attention": ("mfma", ("mg_attn_fwd", "mg_attn_bwd", "mg_xattn_fwd", "mg_xattn_bwd")),
+    "attention": ("mfma", ("mg_attn_fwd", "mg_attn_bwd", "mg_xattn_fwd", "mg_xattn_bwd", "mg_xattn_ragged_fwd",
+                          "mg_xattn_ragged_bwd")),
     "router_fwd": ("hbm", ("mg_router_fwd",)),
     "dispatch_combine": ("hbm", ("mg_gather_rows", "mg_moe_combine")),
     "warp_fwd": ("hbm", ("mg_warp_fwd", "mg_warp_fwd_scaled")),
@@ -138,6 +139,12 @@ def work(name, a):
         return 4.0 * a["B"] * a["Lq"] * a["Lk"] * a["C"]
     if name == "mg_xattn_bwd":  # dV, dP, dQ, dK
         return 8.0 * a["B"] * a["Lq"] * a["Lk"] * a["C"]
+    # packed keys: the work is over the live keys, sum(len) -- on the host that is ``rows`` less the bucket's pad
+    # (fewer than 4 B rows), so ``rows`` stands for it; Lmax only sizes the LDS image
+    if name == "mg_xattn_ragged_fwd":
+        return 4.0 * a["Lq"] * a["rows"] * a["C"]
+    if name == "mg_xattn_ragged_bwd":
+        return 8.0 * a["Lq"] * a["rows"] * a["C"]
     if name == "mg_router_fwd":
         T, C, E, k = a["T"], a["C"], a["E"], a["k"]
         return T * C * ELT[a["dtype"]] + E * C * 4 + T * E * 8 + T * k * 8
@@ -355,6 +362,13 @@ def alg_bytes(name, a):
         e = ELT[a["dtype"]]
         return a["B"] * ((3 * a["Lq"] + 4 * a["Lk"]) * a["C"] * e + a["Lq"] * a["C"] * ELT[a["gout_dtype"]] +
                          a["heads"] * a["Lq"] * 4)
+    if name == "mg_xattn_ragged_fwd":  # q, the live kv rows in; out, lse out
+        e = ELT[a["dtype"]]
+        return (2 * a["B"] * a["Lq"] + 2 * a["rows"]) * a["C"] * e + a["B"] * a["heads"] * a["Lq"] * 4
+    if name == "mg_xattn_ragged_bwd":  # q, kv, out, gout, lse in; gq, gkv (every row below ``rows``) out
+        e = ELT[a["dtype"]]
+        return ((3 * a["B"] * a["Lq"] + 4 * a["rows"]) * a["C"] * e + a["B"] * a["Lq"] * a["C"] * ELT[a["gout_dtype"]] +
+                a["B"] * a["heads"] * a["Lq"] * 4)
     return None
 
 

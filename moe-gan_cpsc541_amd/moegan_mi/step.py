@@ -206,9 +206,15 @@ class TrainStep:
 
     # ---- the step ----
     def step(self, real, text, z, eps_d, eps_g, perm, *, anneal=3.0, lr_g=2e-4, lr_d=2e-4, eff_kl_weight=1e-8,
-             prep=True, acc=1, zero_grads=True, step_optim=True):
+             prep=True, acc=1, zero_grads=True, step_optim=True, text_rows=None, row_off=None, lk_max=None):
         """real [B,3,64,64] fp32 NCHW, text [B,512], z [B,512] fp32 (device); eps_d / eps_g: 3 triples of
         router epsilon tensors; perm [B] int32.  Returns a dict of device tensors.
+
+        ``text_rows`` [rows, 512] (pad rows zero) / ``row_off`` device int32 [B+1] / ``lk_max``: per-token text
+        features in packed form (tokens.pack_tokens).  The generator's attention blocks then attend over each
+        image's token rows (the D-phase forward computes the text side with the prefix, the G-phase forward reuses
+        it) and norm2.* and the q / k rows of cross_attn.in_proj_* receive gradients; the pooled ``text`` still
+        feeds the mapping network and the discriminator, whose phases (and ``perm``) are unchanged.
 
         Gradient accumulation (t2i_moe_gan.py:1272, :1329, :1353, :1413): ``zero_grads`` at the first batch of
         a window, ``step_optim`` at its last; gradients are summed and scaled by 1/acc before clipping.  As in
@@ -224,7 +230,7 @@ class TrainStep:
         x3_prev = ops.set_f32x3(self.cdt == torch.bfloat16 and os.environ.get("MOEGAN_F32X3", "1") == "1")
         try:
             return self._step(real, text, z, eps_d, eps_g, perm, anneal, lr_g, lr_d, eff_kl_weight, prep, acc,
-                              zero_grads, step_optim)
+                              zero_grads, step_optim, text_rows, row_off, lk_max)
         finally:
             ops.fold_defer(False)
             ops.set_f32x3(x3_prev)
@@ -234,7 +240,7 @@ class TrainStep:
             self.ge.guard_flags = None
 
     def _step(self, real, text, z, eps_d, eps_g, perm, anneal, lr_g, lr_d, eff_kl_weight, prep, acc, zero_grads,
-              step_optim):
+              step_optim, text_rows=None, row_off=None, lk_max=None):
         c = self.cfg
         accum = acc > 1
         gs, ds = self.gs, self.ds
@@ -254,7 +260,8 @@ class TrainStep:
         # the router-independent prefix of this forward (mapping, styles, gen_block_4's convolution block) is
         # kept with its saved activations and reused by the G-phase forward: same z / text, G not yet updated
         f16, _, _, probs_d, topi_d, _ = self.ge.forward(z, text, eps_d, anneal, c.psi, train=True, save=False,
-                                                        want_kl=False, keep_prefix=True)
+                                                        want_kl=False, keep_prefix=True, text_rows=text_rows,
+                                                        row_off=row_off, lk_max=lk_max)
         prefix, self.ge.last_prefix = self.ge.last_prefix, None
         dres = self.de.d_phase(real, text, f16, ("nhwc", 8), perm, c.r1_gamma)
         ops.fold_flush()

@@ -247,8 +247,8 @@ class AuroraGenerator(_FlatModule):
         projected to 512): the attention blocks cross-attend over text_projection applied per token instead of the
         one pooled row; ``text_len`` (list or int tensor [B], 1 <= len <= Lk) masks each image's padding tokens.
         The pooled ``text_input`` still feeds the mapping network.  Defaults: the reference's one-token path.
-        Training with tokens goes through this autograd path (the fused TrainStep and the reference dataset layout
-        carry pooled embeddings only)."""
+        This is the padded form of the autograd path; the fused TrainStep trains on the same features in packed
+        form (TrainStep.step(text_rows=...), train_aurora_gan(text_tokens=True))."""
         self._require_gpu()
         text = self.encode_text(text_input)
         B = z.shape[0]
@@ -433,7 +433,13 @@ class _StepRunner:
     captured BEFORE it: a later capture may place its temporaries in blocks that hold an earlier variant's outputs.
     Invariant: a variant's outputs are read or copied (train_aurora_gan: _stats_to_host, in stream order right after
     the replay) before any other variant replays.  tests/test_loop_gpu.py checks the returned values across the
-    variant switches of an acc > 1 window and measures the loop's peak memory."""
+    variant switches of an acc > 1 window and measures the loop's peak memory.
+
+    A token batch (``text_rows`` / ``row_off`` / ``lk_max``, moegan_mi.tokens) adds its two buckets (rows, lk_max)
+    to the variant key, with static buffers for the packed rows and the offsets.  At most ``MAX_TOKEN_VARIANTS``
+    token variants are kept per epoch; a batch that would need one more runs eagerly."""
+
+    MAX_TOKEN_VARIANTS = 8
 
     def __init__(self, ts, device, enabled=True):
         self.ts = ts
@@ -457,12 +463,21 @@ class _StepRunner:
             self.pool = None  # (a released pool cannot be captured into again: the next capture makes a new one)
             self.epoch_key = ekey
         key = (kw.get("zero_grads", True), kw.get("step_optim", True))
+        text_rows, row_off = kw.get("text_rows"), kw.get("row_off")
+        if text_rows is not None:
+            key += (int(text_rows.shape[0]), int(kw["lk_max"]))
         ent = self.graphs.get(key)
         if ent is None:
+            if text_rows is not None and sum(len(k) > 2 for k in self.graphs) >= self.MAX_TOKEN_VARIANTS:
+                return self.ts.step(real, text, z, eps_d, eps_g, perm, **kw)
             bufs = dict(real=real.clone(), text=text.clone(), z=z.clone(),
                         eps_d=[tuple(t.clone() for t in trip) for trip in eps_d], eps_g=eps_g, perm=perm.clone())
+            kws = dict(kw)
+            if text_rows is not None:
+                bufs.update(text_rows=text_rows.clone(), row_off=row_off.clone())
+                kws.update(text_rows=bufs["text_rows"], row_off=bufs["row_off"])
 
-            def fn(b=bufs):
+            def fn(b=bufs, kw=kws):
                 return self.ts.step(b["real"], b["text"], b["z"], b["eps_d"], b["eps_g"], b["perm"], **kw)
             if self.stream is None:
                 self.stream = torch.cuda.Stream()
@@ -478,6 +493,9 @@ class _StepRunner:
             b["text"].copy_(text)
             b["z"].copy_(z)
             b["perm"].copy_(perm)
+            if text_rows is not None:
+                b["text_rows"].copy_(text_rows)
+                b["row_off"].copy_(row_off)
             for dst, src in zip(b["eps_d"], eps_d):
                 for x, y in zip(dst, src):
                     x.copy_(y)
@@ -517,7 +535,7 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
                      gradient_accumulation_steps=8, checkpoint_activation=True, batch_memory_limit=20.0,
                      max_resolution=16, *, clip_weight_64=None, clip_weight_32=None, num_experts=NUM_EXPERTS,
                      topk=None, dtype=None, process_group=None, seed=0, resume_from=None, save_every_epoch=False,
-                     use_graphs=True, on_batch_done=None):
+                     use_graphs=True, on_batch_done=None, text_tokens=False, max_text_tokens=None):
     """Reference :1029-1669.  ``clip_weight_64``/``clip_weight_32`` (the names train_model.py passes,
     SURVEY.md §0) map to the 16x16 / 8x8 CLIP weights.  ``use_amp`` selects bf16 (the MI355X mixed
     precision; the reference's fp16 GradScaler is not needed) unless ``dtype`` is given.
@@ -534,6 +552,11 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
     ``use_graphs``: every batch body is a replayed hipGraph (``_StepRunner``, bench.py's launch mode).
     ``on_batch_done(epoch, batch_idx, flags)``: called when a batch's results have reached the host (bench.py
     --loop); ``flags`` is the batch's guard word (bit 0: non-finite D loss, bit 1: non-finite G loss).
+    ``text_tokens``: the loaders yield (images, text, text_rows, row_off, lk_max) batches (moegan_mi.tokens:
+    ProcessedTokenDataset / collate_tokens) and the generator's cross-attention trains on each caption's token
+    rows, through the same captured step; validation feeds the same rows to the generator module.
+    ``max_text_tokens``: the caption length the loaders were built with (ProcessedTokenDataset truncates); a
+    batch whose key bucket exceeds it is an error.
     ``resume_from``: a resume checkpoint (:1484-1491 layout, ours or the reference's) to start from;
     ``save_every_epoch``: write that layout after every epoch (the reference's commented-out :1642-1652).
 
@@ -626,7 +649,18 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
                                   "KL": f"{kl:.4f}", "Balance": f"{bal:.4f}", "Clip16": f"{c16:.3f}",
                                   "Clip8": f"{c8:.3f}"})
             step += 1
-        for batch_idx, (real, text) in enumerate(pbar):
+        for batch_idx, batch in enumerate(pbar):
+            real, text = batch[0], batch[1]
+            tok_kw = {}
+            if text_tokens:
+                if len(batch) != 5:
+                    raise ValueError("text_tokens=True needs (images, text, text_rows, row_off, lk_max) batches "
+                                     "(moegan_mi.tokens.collate_tokens)")
+                tok_kw = dict(text_rows=batch[2].to(device, non_blocking=True).float(),
+                              row_off=batch[3].to(device, non_blocking=True).int(), lk_max=int(batch[4]))
+                if max_text_tokens is not None and tok_kw["lk_max"] > -(-int(max_text_tokens) // 32) * 32:
+                    raise ValueError(f"a batch with captions of up to {tok_kw['lk_max']} tokens: the dataset was "
+                                     f"not built with max_tokens={max_text_tokens}")
             real = real.to(device, non_blocking=True).float()
             text = text.to(device, non_blocking=True).float()
             B = real.shape[0]
@@ -637,7 +671,7 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
             zero = batch_idx % acc == 0
             stp = (batch_idx + 1) % acc == 0 or (batch_idx + 1) == n_batches
             out = runner(real, text, z, eps_d, eps_g, perm, anneal=temperature_factor, lr_g=cur_lr, lr_d=cur_lr,
-                         eff_kl_weight=eff_kl, acc=acc, zero_grads=zero, step_optim=stp)
+                         eff_kl_weight=eff_kl, acc=acc, zero_grads=zero, step_optim=stp, **tok_kw)
             if device.type == "cuda":
                 rec = _stats_to_host(out) + (batch_idx,)
             else:
@@ -702,11 +736,16 @@ def _validate(generator, discriminator, loader, gan_loss, temperature_factor, ef
     keys = ("val_d_loss", "val_g_loss", "val_clip_loss_16", "val_clip_loss_8")
     tot = torch.zeros(len(keys) + 1, dtype=torch.float64)
     with torch.no_grad():
-        for real, text in loader:
-            real, text = real.to(device).float(), text.to(device).float()
+        for batch in loader:
+            real, text = batch[0].to(device).float(), batch[1].to(device).float()
             B = real.shape[0]
             z = torch.randn(B, LATENT_DIM, device=device, generator=gen)
-            f16, f8, kl = generator(z, text, return_intermediate=True, annealing_factor=temperature_factor)
+            tok_kw = {}
+            if len(batch) == 5:  # a token batch (moegan_mi.tokens.collate_tokens): the module takes the padded form
+                from moegan_mi.tokens import unpack_tokens
+                tok, tlen = unpack_tokens(batch[2].to(device).float(), batch[3].to(device), int(batch[4]))
+                tok_kw = dict(text_tokens=tok, text_len=tlen)
+            f16, f8, kl = generator(z, text, return_intermediate=True, annealing_factor=temperature_factor, **tok_kw)
             rp = discriminator(real, text)
             fp = discriminator(f16, text)
             mp = discriminator(real, text[torch.randperm(B, device=device, generator=gen)])

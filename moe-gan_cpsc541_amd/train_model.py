@@ -91,6 +91,11 @@ def parse_args(argv=None):
     p.add_argument("--hyperparameters", type=str, default=None,
                    help="SageMaker-style hyperparameters.json (string values, sagemaker_train.py:85-102); batch_size "
                         "and the train_aurora_gan keys override the flags above, other keys are reported as unused")
+    p.add_argument("--text_tokens", action="store_true",
+                   help="train the generator's cross-attention on per-token text features: reads *_text_tokens.npy / "
+                        "*_text_len.npy (encode_captions --tokens) beside each *_text_embeddings.npy")
+    p.add_argument("--max_text_tokens", type=int, default=None,
+                   help="with --text_tokens: keep each caption's first N token rows only")
     return p.parse_args(argv)
 
 
@@ -124,22 +129,31 @@ def main(argv=None):
     if not os.path.exists(tr_i) or not os.path.exists(tr_e):
         print(f"Error: Training data not found at {tr_i} or {tr_e}")
         sys.exit(1)
-    val_ds = ProcessedMSCOCODataset(va_i, va_e) if os.path.exists(va_i) and os.path.exists(va_e) else None
+    collate = None
+    if args.text_tokens:  # (image, pooled text, live token rows) items, packed per batch; a missing file is an error
+        from moegan_mi.tokens import ProcessedTokenDataset, collate_tokens
+        collate = collate_tokens
+
+        def make_ds(images_file, embeddings_file):
+            return ProcessedTokenDataset(images_file, embeddings_file, max_tokens=args.max_text_tokens)
+    else:
+        make_ds = ProcessedMSCOCODataset
+    val_ds = make_ds(va_i, va_e) if os.path.exists(va_i) and os.path.exists(va_e) else None
     if val_ds is None:
         print(f"Warning: Validation data not found at {va_i} or {va_e}. Skipping validation.")
-    train_ds = ProcessedMSCOCODataset(tr_i, tr_e)
+    train_ds = make_ds(tr_i, tr_e)
     sampler = None
     if world > 1:
         from torch.utils.data.distributed import DistributedSampler
         sampler = DistributedSampler(train_ds, num_replicas=world, rank=rank, shuffle=True, drop_last=True)
     workers = max(1, min(8, (os.cpu_count() or 2) // 2))
     train_dl = DataLoader(train_ds, batch_size=args.batch_size, shuffle=sampler is None, sampler=sampler,
-                          num_workers=workers, pin_memory=True, drop_last=True)
+                          num_workers=workers, pin_memory=True, drop_last=True, collate_fn=collate)
     val_dl = None
     if val_ds is not None:  # every rank validates its shard; the sums are all-reduced inside the loop
         vs = ShardSampler(len(val_ds), rank, world) if world > 1 else None
         val_dl = DataLoader(val_ds, batch_size=args.batch_size, shuffle=False, sampler=vs, num_workers=workers,
-                            pin_memory=True)
+                            pin_memory=True, collate_fn=collate)
     kw = dict(num_epochs=args.epochs, lr=args.lr, beta1=args.beta1, beta2=args.beta2, r1_gamma=args.r1_gamma,
               clip_weight_16=args.clip_weight_64, clip_weight_8=args.clip_weight_32, kl_weight=args.kl_weight,
               balance_weight=args.balance_weight, log_interval=args.log_interval, save_interval=args.save_interval,
@@ -153,6 +167,8 @@ def main(argv=None):
     if args.clip_weights:
         M.load_clip_weights(args.clip_weights, device)
     kw.setdefault("max_resolution", args.max_resolution)
+    if args.text_tokens:
+        kw.update(text_tokens=True, max_text_tokens=args.max_text_tokens)
     G, D = M.train_aurora_gan(train_dl, val_dataloader=val_dl, device=device, save_dir=args.save_dir,
                               num_experts=args.num_experts, topk=args.topk, dtype=args.dtype, process_group=pg,
                               resume_from=args.resume, save_every_epoch=args.save_every_epoch, **kw)
