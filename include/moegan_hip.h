@@ -56,6 +56,7 @@ extern "C" {
 #define MG_ACT_MUL_LRELU_GRAD 4 /* v *= LReLU'(aux[m,n]) */
 #define MG_ACT_RSQRT_EPS 5      /* v = rsqrt(v + 1e-8)  (demodulation, t2i_moe_gan.py:165) */
 #define MG_ACT_QUICK_GELU 6     /* v * sigmoid(1.702 v)  (CLIP ViT MLP, forward-only CLIP loss :66-119) */
+#define MG_ACT_MUL_QUICK_GELU_GRAD 7 /* v *= QuickGELU'(aux[m,n])  (the CLIP tower's data gradient) */
 
 /* Fused GEMM epilogue / prologue options (all pointers optional = NULL).
  *   v = alpha * acc
@@ -254,10 +255,19 @@ int mg_moe_ffn_bwd(int dtype, int total_rows, int C, int Hd, int ngroups, const 
    R->res (align_corners=False) from NHWC [B,R,R,ld] (channels 0..2), unfolded patch rows [B*(res/patch)^2, 3*patch*patch] bf16. */
 int mg_clip_patches(int dtype, const void* img, int B, int R, int ld, int res, int patch, void* out, void* stream);
 
+/* Adjoint of mg_clip_patches: g_patches [B*(res/patch)^2, 3*patch*patch] (fp32 or bf16) -> g_img NHWC [B,R,R,ld] of
+   the image's dtype, channels 0..2 (=) or (+=) alpha * gradient, pad channels untouched; zero where the image lies
+   outside [-1, 1] (the clamp).  One writer per element, fixed summation order (no atomics). */
+int mg_clip_patches_bwd(int g_dtype, const void* g_patches, int img_dtype, const void* img, int B, int R, int ld, int res, int patch, float alpha, int accumulate, void* g_img, void* stream);
+
+/* CLIP loss 1 - mean_b nan_to_num(cos(f_b, text_b)) over fp32 rows [B, C] (C = 64 or 512) and its feature gradient
+   g_f = -(scale[0] / B) (t^ - cos f^) / |f| (zero rows where the similarity is not finite); scale is a device scalar. */
+int mg_cos_loss(const float* f, const float* text, int B, int C, const float* scale, float* loss, float* g_f, void* stream);
+
 /* LayerNorm over C (128/256/512) per row (+ optional LeakyReLU), saving mean/rstd. t2i_moe_gan.py:505-507, :684. */
 int mg_layernorm_fwd(int dtype, const void* x, int64_t ldx, int R, int C, const float* gamma, const float* beta, float eps, void* y, int64_t ldy, float* mean, float* rstd, int act, void* stream);
 
-/* LayerNorm backward (gx (+)=, ggamma/gbeta += via atomics). */
+/* LayerNorm backward (gx (+)=, ggamma/gbeta += via atomics).  C = 768 (the CLIP tower): gx only, ggamma = gbeta = NULL. */
 int mg_layernorm_bwd(int dtype, int gy_dtype, const void* gy, int64_t ldg, const void* x, int64_t ldx, int R, int C, const float* mean, const float* rstd, const float* gamma, void* gx, int64_t ldgx, int accumulate, float* ggamma, float* gbeta, void* stream);
 
 /* Self-attention core for nn.MultiheadAttention (8 heads) on packed qkv [B*L, 3C]; saves logsumexp. t2i_moe_gan.py:513, :546. */

@@ -385,6 +385,63 @@ __global__ __launch_bounds__(256) void k_ln_bwd_v(const TG* __restrict__ gy, int
   }
 }
 
+// 4 consecutive elements -> float[4] (8-B aligned bf16, 16-B aligned fp32) and back
+MG_DEV void ld4(const float* p, float* t) {
+  const f32x4_t a = *reinterpret_cast<const f32x4_t*>(p);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) t[j] = a[j];
+}
+MG_DEV void ld4(const bf16_t* p, float* t) {
+  const u16x4_t a = *reinterpret_cast<const u16x4_t*>(p);
+#pragma unroll
+  for (int j = 0; j < 4; ++j) t[j] = bf2f(a[j]);
+}
+MG_DEV void st4(float* p, const float* v) { *reinterpret_cast<f32x4_t*>(p) = f32x4_t{v[0], v[1], v[2], v[3]}; }
+MG_DEV void st4(bf16_t* p, const float* v) {
+  *reinterpret_cast<u16x4_t*>(p) = u16x4_t{f2bf(v[0]), f2bf(v[1]), f2bf(v[2]), f2bf(v[3])};
+}
+
+// C = 768 (the CLIP image tower), data gradient only: one wave per row, the row held as one 8-wide vector per lane
+// (channels 8 * lane, 0..511) plus one 4-wide (512 + 4 * lane), so every access is a whole 8 / 16-B vector and the
+// 768-term sums are two wave reductions.  No gamma / beta gradient (the tower is frozen): nothing crosses rows.
+template <typename T, typename TG>
+__global__ __launch_bounds__(256) void k_ln_bwd_768(const TG* __restrict__ gy, int64_t ldg, const T* __restrict__ x,
+                                                    int64_t ldx, int R, const float* __restrict__ mean,
+                                                    const float* __restrict__ rstd, const float* __restrict__ gamma,
+                                                    T* __restrict__ gx, int64_t ldgx, int accumulate) {
+  constexpr int C = 768;
+  const int lane = threadIdx.x & 63;
+  const int r = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
+  if (r >= R) return;  // wave-uniform
+  const int ca = lane * 8, cb = 512 + lane * 4;
+  float g[12], xh[12], ga[12], o[12];
+  ld8(gy + (int64_t)r * ldg + ca, g);
+  ld4(gy + (int64_t)r * ldg + cb, g + 8);
+  ld8(x + (int64_t)r * ldx + ca, xh);
+  ld4(x + (int64_t)r * ldx + cb, xh + 8);
+  ld8(gamma + ca, ga);
+  ld4(gamma + cb, ga + 8);
+  if (accumulate) {
+    ld8(gx + (int64_t)r * ldgx + ca, o);
+    ld4(gx + (int64_t)r * ldgx + cb, o + 8);
+  }
+  const float mu = mean[r], rs = rstd[r];
+  float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+  for (int j = 0; j < 12; ++j) {
+    xh[j] = (xh[j] - mu) * rs;
+    g[j] *= ga[j];
+    s1 += g[j];
+    s2 += g[j] * xh[j];
+  }
+  s1 = wave_sum(s1) / C;
+  s2 = wave_sum(s2) / C;
+#pragma unroll
+  for (int j = 0; j < 12; ++j) o[j] = rs * (g[j] - s1 - xh[j] * s2) + (accumulate ? o[j] : 0.f);
+  st8(gx + (int64_t)r * ldgx + ca, o);
+  st4(gx + (int64_t)r * ldgx + cb, o + 8);
+}
+
 }  // namespace
 
 extern "C" int mg_layernorm_fwd(int dtype, const void* x, int64_t ldx, int R, int C, const float* gamma,
@@ -420,8 +477,26 @@ extern "C" int mg_layernorm_fwd(int dtype, const void* x, int64_t ldx, int R, in
 extern "C" int mg_layernorm_bwd(int dtype, int gy_dtype, const void* gy, int64_t ldg, const void* x, int64_t ldx,
                                 int R, int C, const float* mean, const float* rstd, const float* gamma, void* gx,
                                 int64_t ldgx, int accumulate, float* ggamma, float* gbeta, void* stream) {
-  MG_REQUIRE(C == 128 || C == 256 || C == 512, "C must be 128, 256 or 512");
+  MG_REQUIRE(C == 128 || C == 256 || C == 512 || C == 768, "C must be 128, 256, 512 or 768");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (C == 768) {  // the CLIP image tower's width: data gradient only (clip_vit.py backward)
+    MG_REQUIRE(!ggamma && !gbeta && gx, "C = 768 computes the data gradient only (ggamma = gbeta = NULL, gx set)");
+    MG_REQUIRE(ldg % 8 == 0 && ldx % 8 == 0 && ldgx % 8 == 0 && mg_al16(gy) && mg_al16(x) && mg_al16(gx) &&
+                   mg_al16(gamma),
+               "C = 768 needs 16-byte aligned rows");
+    MG_REQUIRE(R >= 0, "bad row count");
+    if (R == 0) return MG_OK;
+    dim3 g7(cdiv(R, 4)), b7(256);
+#define L7_(T, TG) hipLaunchKernelGGL((k_ln_bwd_768<T, TG>), g7, b7, 0, st, (const TG*)gy, ldg, (const T*)x, ldx, R, mean, \
+                                      rstd, gamma, (T*)gx, ldgx, accumulate)
+    if (dtype == MG_F32) {
+      if (gy_dtype == MG_F32) L7_(float, float); else L7_(float, bf16_t);
+    } else {
+      if (gy_dtype == MG_F32) L7_(bf16_t, float); else L7_(bf16_t, bf16_t);
+    }
+#undef L7_
+    return mg_check_launch("mg_layernorm_bwd");
+  }
   if (R == 0) return MG_OK;
   if (ldg % 8 == 0 && ldx % 8 == 0 && (!gx || ldgx % 8 == 0) && mg_al16(gy) && mg_al16(x) && (!gx || mg_al16(gx)) &&
       mg_al16(gamma)) {
@@ -592,4 +667,148 @@ extern "C" int mg_clip_patches(int dtype, const void* img, int B, int R, int ld,
     hipLaunchKernelGGL((k_clip_patches<bf16_t, 32>), dim3(rows), dim3(3 * 32 * 32 / 8), 0, st, (const bf16_t*)img, R,
                        ld, res, (bf16_t*)out);
   return mg_check_launch("mg_clip_patches");
+}
+
+// ---------------------------------------------------------------------------
+// Adjoint of mg_clip_patches: d loss / d generator image from the gradient of the unfolded patch rows.
+// Gather form: thread (b, c, y, x) owns one source element and sums, in a fixed order, over the destination pixels
+// whose bilinear footprint includes it, so there is one writer per element and no atomic in either library mode.
+// Destination d reads sources y0 = floor(src(d)) and y1 = y0 + (y0 < R - 1) with src(d) = max(0, (d + 0.5) R / res
+// - 0.5): source y is touched by the d with src(d) in [y - 1, y + 1), i.e. d in [(y - 0.5) res / R - 0.5,
+// (y + 1.5) res / R - 0.5) -- at most 2 res / R + 1 values; the low edge (src clamped to 0) and the high edge
+// (y1 == y0 == R - 1, both weights on one source) fall inside it after the clamp to [0, res).  The range is widened
+// by one on each side and every candidate's (y0, y1, weights) is recomputed with the forward's own float
+// expressions, a source taking only the weights whose index equals it: rounding in the analytic bounds cannot drop
+// or add a term; a candidate of weight 0 is skipped, not multiplied.  Row sums are formed in their own accumulator before they join the pixel's sum.
+// Clamp mask as torch.clamp's backward: the gradient passes where -1 <= v <= 1 (NaN: no).
+// ---------------------------------------------------------------------------
+namespace {
+template <typename TG, typename T, int P>
+__global__ __launch_bounds__(256) void k_clip_patches_bwd(const TG* __restrict__ gp, const T* __restrict__ img, int B,
+                                                          int R, int ld, int res, float alpha, int accumulate,
+                                                          T* __restrict__ gimg) {
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (int64_t)B * 3 * R * R) return;
+  const int x = (int)(idx % R), y = (int)((idx / R) % R), c = (int)((idx / ((int64_t)R * R)) % 3);
+  const int b = (int)(idx / (3LL * R * R));
+  const int64_t off = (((int64_t)b * R + y) * R + x) * ld + c;
+  const float v = ldf(img, off);
+  float acc = 0.f;
+  if (v >= -1.f && v <= 1.f) {
+    const int g = res / P;
+    const float scale = (float)R / (float)res, inv = (float)res / (float)R;
+    auto lo = [&](int s) { return min(max((int)floorf((s - 0.5f) * inv - 0.5f) - 1, 0), res - 1); };
+    auto hi = [&](int s) { return min(max((int)ceilf((s + 1.5f) * inv - 0.5f) + 1, 0), res - 1); };
+    // weight of source s in destination d (the forward's expressions)
+    auto wgt = [&](int d, int s) {
+      const float sf = fmaxf(scale * (d + 0.5f) - 0.5f, 0.f);
+      const int s0 = (int)sf, s1 = s0 + (s0 < R - 1 ? 1 : 0);
+      const float l1 = sf - s0, l0 = 1.f - l1;
+      return (s0 == s ? l0 : 0.f) + (s1 == s ? l1 : 0.f);
+    };
+    const int dy0 = lo(y), dy1 = hi(y), dx0 = lo(x), dx1 = hi(x);
+    for (int dy = dy0; dy <= dy1; ++dy) {
+      const float wy = wgt(dy, y);
+      if (wy == 0.f) continue;
+      const int64_t rowbase = ((int64_t)b * g + dy / P) * g;
+      const int colbase = (c * P + dy % P) * P;
+      float rsum = 0.f;
+      for (int dx = dx0; dx <= dx1; ++dx) {
+        const float wx = wgt(dx, x);
+        if (wx == 0.f) continue;  // outside the footprint: not read (a non-finite neighbour must not reach this pixel)
+        rsum += wx * ldf(gp, (rowbase + dx / P) * (3 * P * P) + colbase + dx % P);
+      }
+      acc += wy * rsum;
+    }
+  }
+  acc *= alpha;
+  if (accumulate) acc += ldf(gimg, off);
+  stf(gimg, off, acc);
+}
+
+// 1 - mean_b nan_to_num(cos(f_b, t_b)) and its gradient with respect to f, one launch, one block: wave w walks
+// rows w, w + nw, ... (a row's three dot products are wave reductions), keeps its similarities' sum in row order,
+// and the waves' sums are added in wave order -- a fixed order, so two calls agree bit for bit.
+// g_f[b] = -(scale / B) (t^_b - cos_b f^_b) / |f_b|; a row whose similarity is not finite adds 0 to the mean and
+// gets a zero gradient row (nan_to_num's value, and its zero derivative there).
+template <int NPL>  // C = 64 * NPL
+__global__ __launch_bounds__(1024) void k_cos_loss(const float* __restrict__ f, const float* __restrict__ t, int B,
+                                                   const float* __restrict__ scale, float* __restrict__ loss,
+                                                   float* __restrict__ gf) {
+  constexpr int C = 64 * NPL;
+  __shared__ float ws[16];
+  const int lane = threadIdx.x & 63, w = threadIdx.x >> 6, nw = blockDim.x >> 6;
+  const float k = scale[0] / (float)B;
+  float part = 0.f;
+  for (int r = w; r < B; r += nw) {
+    float fv[NPL], tv[NPL], ff = 0.f, tt = 0.f, ft = 0.f;
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) {
+      fv[i] = f[(int64_t)r * C + lane + 64 * i];
+      tv[i] = t[(int64_t)r * C + lane + 64 * i];
+    }
+#pragma unroll
+    for (int i = 0; i < NPL; ++i) {
+      ff += fv[i] * fv[i];
+      tt += tv[i] * tv[i];
+      ft += fv[i] * tv[i];
+    }
+    ff = wave_sum(ff);
+    tt = wave_sum(tt);
+    ft = wave_sum(ft);
+    const float nf = sqrtf(ff), nt = sqrtf(tt);
+    const float cs = ft / (nf * nt);
+    const bool ok = isfinite(cs);
+    part += ok ? cs : 0.f;
+    const float a = ok ? -k / (nf * nt) : 0.f, bq = ok ? k * cs / ff : 0.f;  // g = a t + bq f
+#pragma unroll
+    for (int i = 0; i < NPL; ++i)
+      gf[(int64_t)r * C + lane + 64 * i] = ok ? a * tv[i] + bq * fv[i] : 0.f;
+  }
+  if (lane == 0) ws[w] = part;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    float s = 0.f;
+    for (int i = 0; i < nw; ++i) s += ws[i];
+    loss[0] = 1.f - s / (float)B;
+  }
+}
+}  // namespace
+
+extern "C" int mg_clip_patches_bwd(int g_dtype, const void* g_patches, int img_dtype, const void* img, int B, int R,
+                                   int ld, int res, int patch, float alpha, int accumulate, void* g_img,
+                                   void* stream) {
+  MG_REQUIRE(g_dtype == MG_F32 || g_dtype == MG_BF16, "bad g_patches dtype");
+  MG_REQUIRE(img_dtype == MG_F32 || img_dtype == MG_BF16, "bad image dtype");
+  MG_REQUIRE(patch == 32, "patch must be 32 (ViT-B/32)");
+  MG_REQUIRE(B >= 0 && R >= 1 && res >= patch && R <= res && ld >= 3 && res % patch == 0,
+             "bad clip patch geometry (1 <= R <= res, ld >= 3, res a multiple of patch)");
+  MG_REQUIRE((int64_t)B * (res / patch) * (res / patch) < (1LL << 31) && (int64_t)B * 3 * R * R < (1LL << 31) &&
+                 (int64_t)R * ld < (1LL << 31),
+             "too many pixels");
+  MG_REQUIRE(g_patches && img && g_img, "null pointer");
+  if (B == 0) return MG_OK;
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  dim3 grid(cdiv((int64_t)B * 3 * R * R, 256)), blk(256);
+#define L_(TG, T) hipLaunchKernelGGL((k_clip_patches_bwd<TG, T, 32>), grid, blk, 0, st, (const TG*)g_patches, \
+                                     (const T*)img, B, R, ld, res, alpha, accumulate, (T*)g_img)
+  if (g_dtype == MG_F32) {
+    if (img_dtype == MG_F32) L_(float, float); else L_(float, bf16_t);
+  } else {
+    if (img_dtype == MG_F32) L_(bf16_t, float); else L_(bf16_t, bf16_t);
+  }
+#undef L_
+  return mg_check_launch("mg_clip_patches_bwd");
+}
+
+extern "C" int mg_cos_loss(const float* f, const float* text, int B, int C, const float* scale, float* loss,
+                           float* g_f, void* stream) {
+  MG_REQUIRE(C == 64 || C == 512, "C must be 64 or 512");
+  MG_REQUIRE(B >= 1, "B must be at least 1");
+  MG_REQUIRE(f && text && scale && loss && g_f, "null pointer");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  const int nw = std::min(16, B);
+  if (C == 64) hipLaunchKernelGGL((k_cos_loss<1>), dim3(1), dim3(64 * nw), 0, st, f, text, B, scale, loss, g_f);
+  else hipLaunchKernelGGL((k_cos_loss<8>), dim3(1), dim3(64 * nw), 0, st, f, text, B, scale, loss, g_f);
+  return mg_check_launch("mg_cos_loss");
 }

@@ -119,14 +119,19 @@ __global__ __launch_bounds__(256) void k_attn_fwd_mfma(const bf16_t* __restrict_
 // ---------------------------------------------------------------------------
 // backward: dQ (query-owner waves), then dK, dV (key-owner waves)
 // ---------------------------------------------------------------------------
-template <int D, int L, int U>
+// LT: token tile length; MASK: a runtime sequence length Lrt < LT (CLIP's 50 tokens on the 64-token tiles, as in the
+// forward): rows past L are staged as zeros, their probabilities are zeroed (key slots in the dQ pass, query slots in
+// the dK / dV pass: the zeroed rows' Ls = Ds = 0 keep exp2 finite) and only live rows are stored.  With MASK false
+// (the generator's blocks) L is the compile-time LT, Lrt is not read and the code is the unmasked kernel's.
+template <int D, int LT, int U, bool MASK>
 __global__ __launch_bounds__(256) void k_attn_bwd_mfma(const bf16_t* __restrict__ qkv, const bf16_t* __restrict__ out,
                                                        const bf16_t* __restrict__ gout, const float* __restrict__ lse,
-                                                       int B, int C, int heads, bf16_t* __restrict__ gqkv) {
+                                                       int B, int C, int heads, bf16_t* __restrict__ gqkv, int Lrt) {
   constexpr int P = Pitch<D>::P;
-  constexpr int Lp = L < 32 ? 32 : L;
-  constexpr int WPU = L / 16 < 4 ? L / 16 : 4;
+  constexpr int Lp = LT < 32 ? 32 : LT;
+  constexpr int WPU = LT / 16 < 4 ? LT / 16 : 4;
   constexpr int NB = Lp / 16;
+  const int L = MASK ? Lrt : LT;
   extern __shared__ __attribute__((aligned(16))) bf16_t smem[];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, g = lane >> 4, fr = lane & 15;
   const int ul = wave / WPU, wu = wave % WPU;
@@ -168,10 +173,10 @@ __global__ __launch_bounds__(256) void k_attn_bwd_mfma(const bf16_t* __restrict_
   __syncthreads();
   if (!live) return;
   const float scale = rsqrtf((float)D), k2 = scale * 1.4426950408889634f;
-  constexpr bool MASKK = Lp != L;  // token slots past L exist only when L < 32
+  constexpr bool MASKK = MASK || Lp != LT;  // token slots past L: a masked launch, or the 16-token tiles' 32 slots
   bf16_t* grow = gqkv + (int64_t)b * L * ld + h * D;
   // ---- pass A: dQ = scale * dS K for query tiles
-  for (int t = wu; t < L / 16; t += WPU) {
+  for (int t = wu; t < LT / 16; t += WPU) {
     Frag<D> qf = ldfrag<D>(Qs, t * 16 + fr, g), gf = ldfrag<D>(Gs, t * 16 + fr, g);
     const float li = Ls[t * 16 + fr], di = Ds[t * 16 + fr];  // this lane's query column
     f32x4_t dq[D / 16];
@@ -200,10 +205,12 @@ __global__ __launch_bounds__(256) void k_attn_bwd_mfma(const bf16_t* __restrict_
 #pragma unroll
     for (int db = 0; db < D / 16; ++db)
 #pragma unroll
-      for (int r = 0; r < 4; ++r) grow[(int64_t)(t * 16 + 4 * g + r) * ld + db * 16 + fr] = f2bf(dq[db][r] * scale);
+      for (int r = 0; r < 4; ++r)
+        if (!MASK || t * 16 + 4 * g + r < L)
+          grow[(int64_t)(t * 16 + 4 * g + r) * ld + db * 16 + fr] = f2bf(dq[db][r] * scale);
   }
   // ---- pass B: dV = P^T dO, dK = scale * dS^T Q for key tiles
-  for (int t = wu; t < L / 16; t += WPU) {
+  for (int t = wu; t < LT / 16; t += WPU) {
     Frag<D> kf = ldfrag<D>(Ks, t * 16 + fr, g), vf = ldfrag<D>(Vs, t * 16 + fr, g);
     f32x4_t dk[D / 16], dv[D / 16];
 #pragma unroll
@@ -237,6 +244,7 @@ __global__ __launch_bounds__(256) void k_attn_bwd_mfma(const bf16_t* __restrict_
     for (int db = 0; db < D / 16; ++db)
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
+        if (MASK && t * 16 + 4 * g + r >= L) continue;
         const int64_t o = (int64_t)(t * 16 + 4 * g + r) * ld + db * 16 + fr;
         grow[o + C] = f2bf(dk[db][r] * scale);
         grow[o + 2 * C] = f2bf(dv[db][r]);
@@ -272,13 +280,13 @@ int launch_fwd(const bf16_t* qkv, int B, int C, int heads, bf16_t* out, float* l
                        L, C, heads, out, lse);
   return mg_check_launch("mg_attn_fwd (mfma)");
 }
-template <int D, int L>
+template <int D, int LT, bool MASK = false>
 int launch_bwd(const bf16_t* qkv, const bf16_t* out, const bf16_t* gout, const float* lse, int B, int C, int heads,
-               bf16_t* gqkv, hipStream_t st) {
-  constexpr int P = Pitch<D>::P, Lp = L < 32 ? 32 : L, WPU = L / 16 < 4 ? L / 16 : 4, U = units_bwd<D, L>();
+               bf16_t* gqkv, hipStream_t st, int L = LT) {
+  constexpr int P = Pitch<D>::P, Lp = LT < 32 ? 32 : LT, WPU = LT / 16 < 4 ? LT / 16 : 4, U = units_bwd<D, LT>();
   size_t sm = (size_t)U * (4 * Lp * P + 4 * Lp) * sizeof(bf16_t);
-  hipLaunchKernelGGL((k_attn_bwd_mfma<D, L, U>), dim3(cdiv(B * heads, U)), dim3(64 * U * WPU), sm, st, qkv, out, gout,
-                     lse, B, C, heads, gqkv);
+  hipLaunchKernelGGL((k_attn_bwd_mfma<D, LT, U, MASK>), dim3(cdiv(B * heads, U)), dim3(64 * U * WPU), sm, st, qkv, out,
+                     gout, lse, B, C, heads, gqkv, L);
   return mg_check_launch("mg_attn_bwd (mfma)");
 }
 
@@ -315,5 +323,6 @@ int mg_attn_bwd_mfma(const void* qkv, const void* out, const void* gout, const f
   if (D == 64 && L == 64) return launch_bwd<64, 64>(q, o, g, lse, B, C, heads, gq, st);
   if (D == 32 && L == 16) return launch_bwd<32, 16>(q, o, g, lse, B, C, heads, gq, st);
   if (D == 16 && L == 64) return launch_bwd<16, 64>(q, o, g, lse, B, C, heads, gq, st);
+  if (D == 64 && L > 32 && L < 64) return launch_bwd<64, 64, true>(q, o, g, lse, B, C, heads, gq, st, L);  // CLIP: 50
   return 1;
 }

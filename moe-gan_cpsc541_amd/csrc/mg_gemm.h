@@ -503,10 +503,15 @@ struct LdMCGroupW {
 // Epilogue
 // ---------------------------------------------------------------------------
 enum { ACT_NONE = 0, ACT_LRELU = 1, ACT_GELU = 2, ACT_MUL_GELU_GRAD = 3, ACT_MUL_LRELU_GRAD = 4, ACT_RSQRT_EPS = 5,
-       ACT_QUICK_GELU = 6 };
+       ACT_QUICK_GELU = 6, ACT_MUL_QUICK_GELU_GRAD = 7 /* EpiQuickGeluGrad below, not a branch of Epi */ };
 
 // QuickGELU x * sigmoid(1.702 x) (the CLIP image tower's MLP activation)
 MG_DEV float quick_gelu(float x) { return x / (1.f + __expf(-1.702f * x)); }
+// its derivative s (1 + 1.702 x (1 - s)), s = sigmoid(1.702 x) (the tower's data gradient)
+MG_DEV float quick_gelu_grad(float x) {
+  const float s = 1.f / (1.f + __expf(-1.702f * x));
+  return s * (1.f + 1.702f * x * (1.f - s));
+}
 
 template <typename TO>
 struct Epi {
@@ -680,6 +685,41 @@ struct Epi {
       if (accumulate) v += ldf(C, idx);
       stf(C, idx, v);
     }
+  }
+};
+
+// ACT_MUL_QUICK_GELU_GRAD: v *= QuickGELU'(aux[m, n]), aux the saved pre-activation (the CLIP tower's c_proj data
+// gradient).  An epilogue type of its own rather than one more branch of Epi: as a branch it changed the register
+// allocation of every GEMM kernel and put the grouped expert kernels into scratch (figures: DESIGN.md,
+// "Differentiable CLIP loss"); this way only the three kernels that use it carry it.
+// aux takes the prefetch path of the other *_GRAD activations (pf_kind 1); the residual, if any, is read in place.
+// The host admits no bias / scale / out_pre with it (mg_gemm), so multiplying before Epi's own steps is exact.
+template <typename TO>
+struct EpiQuickGeluGrad : Epi<TO> {
+  typedef Epi<TO> Base;
+  typedef typename Base::Pf Pf;
+  bool host_vec_ok() const {
+    return Base::host_vec_ok() && (reinterpret_cast<uintptr_t>(this->aux) & 15) == 0 && this->ld_aux % 8 == 0;
+  }
+  MG_DEV int pf_kind() const { return 1; }
+  MG_DEV void pf_load(int m, int n, Pf& p) const {
+    if (this->rm_mode == 1) m = this->remap_row(m);
+    const TO* src = this->aux + (int64_t)m * this->ld_aux + n;
+#pragma unroll
+    for (int j = 0; j < Base::OV; ++j)
+      p.v[j] = *reinterpret_cast<const typename Base::ovec_t*>(src + j * VecOf<TO>::N);
+  }
+  __attribute__((always_inline)) MG_DEV void vec8(int m, int n, float* v, const Pf* pf = nullptr) const {
+    float t[8];
+    if (pf) Base::pf_unpack(*pf, t);
+    else ld8(this->aux + (int64_t)(this->rm_mode == 1 ? this->remap_row(m) : m) * this->ld_aux + n, t);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) v[j] *= quick_gelu_grad(t[j]);
+    Base::vec8(m, n, v, nullptr);
+  }
+  MG_DEV void operator()(int m, int n, float v) const {
+    const int mm = this->rm_mode == 1 ? this->remap_row(m) : m;
+    Base::operator()(m, n, v * quick_gelu_grad(ldf(this->aux, (int64_t)mm * this->ld_aux + n)));
   }
 };
 

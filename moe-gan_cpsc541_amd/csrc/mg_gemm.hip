@@ -30,6 +30,16 @@ void run_plain(int M, int N, int K, const void* A, int64_t lda, const void* B, i
   int adiv = (e && e->a_idx_div > 0) ? e->a_idx_div : 1;
   const float* ars = e ? e->a_rowscale : nullptr;
   int agelu = e ? e->a_gelu : 0;
+  // g @ W * QuickGELU'(aux) (bf16 data-gradient shape only, checked by mg_gemm): its own epilogue type
+  if constexpr (AK && !BKc && !XF && !X3 && sizeof(T) == 2 && sizeof(TO) == 2) {
+    if (ep.act == ACT_MUL_QUICK_GELU_GRAD) {
+      EpiQuickGeluGrad<TO> q{ep};
+      LdKC<T> la{reinterpret_cast<const T*>(A), lda, M, K, nullptr, 1, nullptr, 0};
+      LdMC<T> lb{reinterpret_cast<const T*>(B), ldb, N, K, nullptr, 1, nullptr, 0};
+      launch_gemm<T, BM, BN, true, false, 0, false>(la, lb, q, M, N, K, splits, kNoGroup, 0, st);
+      return;
+    }
+  }
   if constexpr (AK) {
     LdKC<T, XF> la{reinterpret_cast<const T*>(A), lda, M, K, aidx, adiv, ars, agelu};
     if constexpr (BKc) {
@@ -174,6 +184,10 @@ extern "C" int mg_gemm(int dtype, int M, int N, int K, const void* A, int64_t ld
   MG_REQUIRE(dtype == MG_F32 || dtype == MG_BF16 || dtype == MG_F32X3, "bad dtype");
   MG_REQUIRE(M >= 0 && N >= 0 && K >= 0, "negative size");
   if (M == 0 || N == 0) return MG_OK;
+  const bool qgg = ep && ep->act == MG_ACT_MUL_QUICK_GELU_GRAD;
+  MG_REQUIRE(!qgg || (dtype == MG_BF16 && c_dtype == MG_BF16 && a_kc && !b_kc && splits <= 1 && ep->aux &&
+                      !ep->bias && !ep->scale && !ep->out_pre && !ep->atomic && !ep->remap_taps && !a_xf(ep)),
+             "MG_ACT_MUL_QUICK_GELU_GRAD: bf16 g [M,K] x W [K,N] -> bf16 with aux, no bias / scale / out_pre / atomic");
   const bool x3 = dtype == MG_F32X3;
   if (x3) dtype = MG_F32;  // fp32 storage; the MFMA products run on split bf16
   const int vec = dtype == MG_F32 ? 4 : 8;
@@ -218,7 +232,7 @@ extern "C" int mg_gemm(int dtype, int M, int N, int K, const void* A, int64_t ld
     if (done) return mg_check_launch("mg_gemm (deterministic split-K slabs)");
     splits = 1;
   }
-  if (splits == 1 && !(ep && ep->atomic) && !g_mg_tune[MG_TUNE_NO_SLABS]) {
+  if (splits == 1 && !(ep && ep->atomic) && !qgg && !g_mg_tune[MG_TUNE_NO_SLABS]) {
     bool done;
     if (x3)
       done = c_dtype == MG_F32 ? run_splitk_slabs<float, float, true>(a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, ep, st)
@@ -339,6 +353,7 @@ extern "C" int mg_gemm_batch(int dtype, int a_kc, int b_kc, int c_dtype, int n, 
     MG_REQUIRE(b_kc ? (q.K % vec == 0) : (q.N % vec == 0), "B vector dim must be a multiple of the vector");
     MG_REQUIRE(!(q.ep && q.ep->atomic) || c_dtype == MG_F32, "atomic epilogue requires fp32 C");
     MG_REQUIRE(!a_xf(q.ep), "A loader transforms (a_idx / a_rowscale / a_gelu) are not supported by mg_gemm_batch");
+    MG_REQUIRE(!q.ep || q.ep->act != MG_ACT_MUL_QUICK_GELU_GRAD, "MG_ACT_MUL_QUICK_GELU_GRAD: mg_gemm only");
     MG_REQUIRE(under2g((a_kc ? (int64_t)q.M : q.K) * q.lda, mdt) &&
                    under2g((b_kc ? (int64_t)q.N : q.K) * q.ldb, mdt) && under2g((int64_t)q.M * q.ldc, c_dtype),
                "an operand exceeds 2 GiB (32-bit buffer offsets)");

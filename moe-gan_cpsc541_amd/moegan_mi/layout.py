@@ -129,10 +129,12 @@ def generator_shapes(E=4, max_res=16):
     return d
 
 
-def frozen_rgb_prefixes(max_res=16):
+def frozen_rgb_prefixes(max_res=16, clip_grad=False):
     """to_rgb layers that never receive a gradient in training: all but the final one (the intermediate image
-    only feeds the gradient-free CLIP loss, :98-101; the lower ones are unused).  Reference: ("to_rgb_8.",)."""
-    return tuple(n + "." for n, _ in rgb_layers(max_res)[:-1])
+    only feeds the gradient-free CLIP loss, :98-101; the lower ones are unused).  Reference: ("to_rgb_8.",).
+    ``clip_grad`` (StepConfig.clip_grad: the CLIP terms carry their gradient): the half-resolution layer trains
+    too, so only the layers below it stay frozen -- none at max_res 16."""
+    return tuple(n + "." for n, _ in rgb_layers(max_res)[:-2 if clip_grad else -1])
 
 
 def discriminator_shapes():

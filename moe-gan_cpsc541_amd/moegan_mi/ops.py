@@ -228,15 +228,19 @@ def linear(x, W, bias=None, act=0, out=None, out_dtype=None, **epk):
     return gemm(x, W, M, N, K, out=out, out_dtype=out_dtype, ep=E(bias=bias, act=act, **epk))
 
 
-def linear_dgrad(g, W, out=None, accumulate=0, out_dtype=None, lrelu_out=None):
+def linear_dgrad(g, W, out=None, accumulate=0, out_dtype=None, lrelu_out=None, quick_gelu_pre=None):
     """gx = g @ W for g [M,N], W [N,K] -> [M,K]; ``lrelu_out`` (the leaky-ReLU output y of the layer below, same
-    dtype and shape as gx): gx *= lrelu'(y) in the epilogue."""
+    dtype and shape as gx): gx *= lrelu'(y) in the epilogue; ``quick_gelu_pre`` (the saved pre-activation x of a
+    QuickGELU below, same dtype and shape as gx): gx *= quickgelu'(x)."""
     M, N = g.shape
     K = W.shape[1]
-    if lrelu_out is not None:
+    aux = lrelu_out if lrelu_out is not None else quick_gelu_pre
+    if aux is not None:
+        assert lrelu_out is None or quick_gelu_pre is None
         odt = out_dtype or g.dtype
-        assert lrelu_out.dtype == odt and tuple(lrelu_out.shape) == (M, K) and lrelu_out.stride(1) == 1
-        ep = E(accumulate=accumulate, act=L.ACT_MUL_LRELU_GRAD, aux=lrelu_out, ld_aux=lrelu_out.stride(0))
+        assert aux.dtype == odt and tuple(aux.shape) == (M, K) and aux.stride(1) == 1
+        act = L.ACT_MUL_LRELU_GRAD if lrelu_out is not None else L.ACT_MUL_QUICK_GELU_GRAD
+        ep = E(accumulate=accumulate, act=act, aux=aux, ld_aux=aux.stride(0))
     else:
         ep = E(accumulate=accumulate)
     return gemm(g, W, M, K, N, b_kc=False, out=out, out_dtype=out_dtype, ep=ep)
@@ -1105,6 +1109,32 @@ def clip_patches(img, res=224, patch=32):
     out = torch.empty(B * g * g, 3 * patch * patch, device=img.device, dtype=torch.bfloat16)
     call("mg_clip_patches", dt(img), ptr(img), B, R, ld, res, patch, ptr(out), S())
     return out
+
+
+def clip_patches_bwd(g_patches, img, g_img, res=224, patch=32, alpha=1.0, accumulate=0):
+    """Adjoint of clip_patches: g_patches [B*(res/patch)^2, 3*patch*patch] (fp32 / bf16) -> g_img NHWC like ``img``
+    (channels 0..2 written or accumulated, scaled by alpha; pad channels untouched), zero where img is outside [-1, 1]
+    (mg_clip_patches_bwd)."""
+    B, R, R2, ld = img.shape
+    g = res // patch
+    assert R == R2 and img.is_contiguous() and g_img.is_contiguous() and g_patches.is_contiguous()
+    assert g_img.shape == img.shape and g_img.dtype == img.dtype
+    assert tuple(g_patches.shape) == (B * g * g, 3 * patch * patch), g_patches.shape
+    call("mg_clip_patches_bwd", dt(g_patches), ptr(g_patches), dt(img), ptr(img), B, R, ld, res, patch, alpha,
+         int(accumulate), ptr(g_img), S())
+    return g_img
+
+
+def cos_loss(f, text, scale, loss=None, g_f=None):
+    """1 - mean_b nan_to_num(cos(f_b, text_b)) and d loss / d f times the device scalar ``scale`` (mg_cos_loss);
+    f, text fp32 [B, C].  Returns (loss [1], g_f [B, C])."""
+    B, C = f.shape
+    assert f.dtype == text.dtype == scale.dtype == torch.float32 and text.shape == f.shape
+    assert f.is_contiguous() and text.is_contiguous()
+    loss = torch.empty(1, device=f.device) if loss is None else loss
+    g_f = torch.empty_like(f) if g_f is None else g_f
+    call("mg_cos_loss", ptr(f), ptr(text), B, C, ptr(scale), ptr(loss), ptr(g_f), S())
+    return loss, g_f
 
 
 def g_loss(fake, out, g, scale=1.0):

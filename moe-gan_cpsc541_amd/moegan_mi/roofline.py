@@ -51,14 +51,15 @@ FAMILIES = {
     "grad_fold": ("hbm", ("mg_fold_flush", "mg_fold_rows_batch", "mg_fold_rows_queue", "mg_fold_defer")),
     "d_conv0": ("hbm", ("mg_d0_fwd", "mg_d0_wgrad", "mg_d0_dgrad")),
     "elementwise": ("hbm", ("mg_cast", "mg_copy2d", "mg_lrelu_mask_mul", "mg_upsample2x_fwd", "mg_upsample2x_bwd",
-                            "mg_const_fwd", "mg_gated_axpy", "mg_select_if", "mg_zero_if", "mg_clip_patches")),
+                            "mg_const_fwd", "mg_gated_axpy", "mg_select_if", "mg_zero_if", "mg_clip_patches",
+                            "mg_clip_patches_bwd")),
     "disc_head": ("hbm", ("mg_disc_head_fwd", "mg_disc_head_gmat", "mg_disc_head_sum", "mg_disc_head_bwd_data",
                           "mg_d_head_fwd", "mg_d_head_bwd",
                           "mg_disc_head_bwd_w", "mg_d_text_bwd")),
     "mtm_bwd_unfused": ("hbm", ("mg_warp_bwd", "mg_offset_head_bwd")),
     # scalar losses, guard words, optimizer prologue: a few hundred bytes each, launch-latency bound
     "losses_flags": ("hbm", ("mg_d_loss", "mg_g_loss", "mg_finite_flag", "mg_flag_window", "mg_kl_coefs", "mg_balance",
-                             "mg_opt_prologue", "mg_guard_update")),
+                             "mg_opt_prologue", "mg_guard_update", "mg_cos_loss")),
 }
 _FAMILY_OF = {e: f for f, (_, es) in FAMILIES.items() for e in es}
 
@@ -95,7 +96,8 @@ KERNELS = [
      "elementwise"),
     (r"k_head_|k_d_text|k_dhead_", "disc_head"),
     (r"k_warp_bwd|k_offset_head", "mtm_bwd_unfused"),
-    (r"k_d_loss|k_g_loss|k_finite_flag|k_flag_window|k_guard_update|k_kl_coefs|k_balance|k_opt_prologue",
+    (r"k_d_loss|k_g_loss|k_finite_flag|k_flag_window|k_guard_update|k_kl_coefs|k_balance|k_opt_prologue|"
+     r"k_cos_loss",
      "losses_flags"),
 ]
 
@@ -290,6 +292,10 @@ def work(name, a):
     if name == "mg_clip_patches":  # the 3 image channels in, bf16 patch rows out
         B, R, res = a["B"], a["R"], a["res"]
         return B * R * R * 3 * ELT[a["dtype"]] + B * res * res * 3 * 2
+    if name == "mg_clip_patches_bwd":  # the patch-row gradient in, the image read for its clamp mask, 3 channels out
+        B, R, res = a["B"], a["R"], a["res"]
+        return (B * res * res * 3 * ELT[a["g_dtype"]]
+                + B * R * R * 3 * ELT[a["img_dtype"]] * (3 if a["accumulate"] else 2))
     if name == "mg_disc_head_fwd":
         return a["B"] * a["Hf"] * a["Hf"] * a["Cf"] * ELT[a["dtype"]] + a["B"] * (a["Hf"] - 3) ** 2 * 4
     if name == "mg_disc_head_gmat":
@@ -314,6 +320,8 @@ def work(name, a):
         return B * (a["No"] * 2 + a["Nf"]) * 8.0 + B * 8
     if name == "mg_g_loss":
         return a["B"] * 8.0
+    if name == "mg_cos_loss":  # features and text in, the feature gradient out
+        return a["B"] * a["C"] * 12.0 + 8
     if name == "mg_finite_flag":
         return 4.0 * a["n"]
     if name == "mg_kl_coefs":

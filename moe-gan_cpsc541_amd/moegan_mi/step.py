@@ -11,6 +11,15 @@ progressive extension every to_rgb but the final one)
 sit in the store's frozen tail and are never updated -- exactly as torch's AdamW skips a
 parameter whose .grad is None.
 
+``StepConfig(clip_grad=True)`` (this build's extension, off by default): the two CLIP terms do carry their gradient.
+The G phase then runs img16 and img8 through the build's image tower with the data-gradient context saved (one
+pass per image, the batches of the gradient-free path, so the logged terms keep its values bit for bit: at a
+small batch a 2B-row pass takes other split-K GEMM forms than a B-row one and rounds differently), forms each term
+and its feature gradient in one launch (mg_cos_loss), and the tower's backward
+(clip_vit.ClipImageEncoder.backward) adds clip_weight_16 * d L_clip / d img16 to the adversarial image gradient and
+writes clip_weight_8 * d L_clip / d img8, which the generator backward takes as ``g_img8``: the half-resolution
+to_rgb then trains, so the store keeps it inside the optimised range (layout.frozen_rgb_prefixes(clip_grad=True)).
+
 Loss guards (t2i_moe_gan.py:1315-1320, :1367-1376, :1396-1404) run on the device: a flag word per step
 (``out["flags"]``) records a non-finite discriminator loss (the whole batch is skipped: no gradient is
 kept, no optimizer steps, no step counters advance) or a non-finite generator loss (replaced by 0: only
@@ -43,7 +52,7 @@ FD, FG = ops.FLAG_D_BAD, ops.FLAG_G_BAD
 class StepConfig:
     def __init__(self, E=4, topk=None, dtype="fp32", r1_gamma=10.0, clip_weight_16=0.1, clip_weight_8=0.05,
                  balance_weight=0.01, beta1=0.5, beta2=0.999, weight_decay=0.01, eps=1e-8, d_clip=0.7, g_clip=0.8,
-                 psi=0.7, fp8=False, max_res=16, deterministic=None):
+                 psi=0.7, fp8=False, max_res=16, deterministic=None, clip_grad=False):
         self.E, self.topk = E, topk
         # generator output resolution: 16 = the reference; 32 / 64 / 128 = the progressive extension (layout.py)
         self.max_res = max_res
@@ -55,6 +64,9 @@ class StepConfig:
         self.beta1, self.beta2, self.weight_decay, self.eps = beta1, beta2, weight_decay, eps
         self.d_clip, self.g_clip = d_clip, g_clip
         self.psi = psi
+        # the CLIP terms train the generator (needs the build's image tower as TrainStep's clip_encoder); False: the
+        # reference's gradient-free terms
+        self.clip_grad = bool(clip_grad)
         # deterministic mode (ops.set_deterministic): None = the MOEGAN_DETERMINISTIC environment switch
         self.deterministic = (os.environ.get("MOEGAN_DETERMINISTIC", "0") == "1") if deterministic is None \
             else bool(deterministic)
@@ -81,8 +93,17 @@ def clip_loss(images_nchw, text, encode_image, images_nhwc=None):
         return (1.0 - sim.mean()).reshape(1)
 
 
+def clip_tower(encoder):
+    """The differentiable image tower behind ``encoder`` (the tower itself or one of its bound methods), or None for
+    a foreign encoder (anything without ``encode_generated`` / ``backward``)."""
+    for obj in (encoder, getattr(encoder, "__self__", None), getattr(encoder, "image", None)):
+        if obj is not None and hasattr(obj, "encode_generated") and hasattr(obj, "backward"):
+            return obj
+    return None
+
+
 class TrainStep:
-    def __init__(self, cfg, device="cuda", process_group=None, gstore=None, dstore=None):
+    def __init__(self, cfg, device="cuda", process_group=None, gstore=None, dstore=None, clip_encoder=None):
         self.cfg = cfg
         self.dev = torch.device(device)
         if getattr(cfg, "deterministic", False):
@@ -90,7 +111,8 @@ class TrainStep:
         self.cdt = torch.bfloat16 if cfg.dtype == "bf16" else torch.float32
         self.gs = gstore if gstore is not None else ParamStore(
             generator_shapes(cfg.E, getattr(cfg, "max_res", 16)), self.dev,
-            frozen_prefixes=frozen_rgb_prefixes(getattr(cfg, "max_res", 16)), shadow_dtype=self.cdt)
+            frozen_prefixes=frozen_rgb_prefixes(getattr(cfg, "max_res", 16), getattr(cfg, "clip_grad", False)),
+            shadow_dtype=self.cdt)
         self.ds = dstore if dstore is not None else ParamStore(discriminator_shapes(), self.dev)
         self.ge = GeneratorEngine(self.gs, cfg.E, cfg.topk, self.cdt, fp8=getattr(cfg, "fp8", False))
         self.de = DiscriminatorEngine(self.ds, self.cdt)
@@ -99,9 +121,30 @@ class TrainStep:
         if process_group is not None:
             import torch.distributed as dist
             self.world = dist.get_world_size(process_group)
-        # optional image encoder for the (gradient-free) CLIP loss terms; images are [B,3,H,W] in [-1, 1]
-        self.clip_encoder = None
+        self.clip_grad = bool(getattr(cfg, "clip_grad", False))
+        if self.clip_grad:
+            half = self.ge.rgb_half + "weight"
+            if self.gs.offsets[half][0] >= self.gs.n_opt:
+                raise ValueError(f"clip_grad=True trains {self.ge.rgb_half[:-1]}, which this parameter store keeps "
+                                 "frozen: build it with layout.frozen_rgb_prefixes(max_res, clip_grad=True)")
+            self._clip_scale = torch.ones(1, device=self.dev)  # device scalar of mg_cos_loss (the weights ride alpha)
+        # optional image encoder for the CLIP loss terms (gradient-free unless cfg.clip_grad); images are
+        # [B,3,H,W] in [-1, 1]
+        self.clip_encoder = clip_encoder
         self.win = torch.zeros(1, device=self.dev, dtype=torch.int32)  # accumulation-window word (mg_flag_window)
+
+    @property
+    def clip_encoder(self):
+        return self._clip_encoder
+
+    @clip_encoder.setter
+    def clip_encoder(self, enc):
+        """With cfg.clip_grad only the build's own tower will do: a foreign encoder is refused here, not mid-step."""
+        self._clip_tower = clip_tower(enc) if enc is not None else None
+        if self.clip_grad and enc is not None and self._clip_tower is None:
+            raise ValueError("clip_grad=True needs the build's image tower (moegan_mi.clip_vit.ClipImageEncoder or "
+                             f"its encode_image) as clip_encoder; {type(enc).__name__} has no backward")
+        self._clip_encoder = enc
 
     # ---- data-parallel reductions ----
     # (collectives stay eager segments when the step is replayed as hipGraphs, graphs.py)
@@ -220,6 +263,8 @@ class TrainStep:
         a window, ``step_optim`` at its last; gradients are summed and scaled by 1/acc before clipping.  As in
         the reference, the generator step's loss also accumulates into the discriminator's gradients, which
         matters only when the D optimizer has not stepped yet in the window (acc > 1)."""
+        if self.clip_grad and self._clip_tower is None:
+            raise ValueError("clip_grad=True: attach the image tower first (TrainStep(..., clip_encoder=tower))")
         ops.ARENA.begin(self.dev)
         ops.COLSUMS.active = True  # bias-gradient column sums batched per backward (flushed below)
         # the library's gradient folds too: one batched launch per backward (ops.fold_flush); MOEGAN_FOLD_DEFER=0
@@ -303,9 +348,25 @@ class TrainStep:
         bal = torch.empty(1, device=self.dev)  # (mg_balance writes it)
         coef = torch.empty(c.E, device=self.dev)
         ops.balance(load, c.E, last.shape[0] * self.world, c.balance_weight, float(self.world), bal, coef)
-        # CLIP terms (t2i_moe_gan.py:1385-1387): forward only, they enter g_loss's value but no gradient
-        clip16 = clip8 = None
-        if self.clip_encoder is not None:
+        # CLIP terms (t2i_moe_gan.py:1385-1387).  Default (the reference): forward only, they enter g_loss's value
+        # but no gradient.  cfg.clip_grad: their image gradients join the generator backward below.
+        clip16 = clip8 = g_img8 = None
+        if self.clip_grad:
+            # each image through the tower with its context saved (the gradient-free path's batches: same logged
+            # values), the term with its feature gradient, then the tower's backward: + clip_weight_16 * dL/d img16
+            # onto the adversarial image gradient, clip_weight_8 * dL/d img8 into the new g_img8
+            tower = self._clip_tower
+            t32 = text.float().contiguous()
+            g_img8 = torch.zeros_like(img8)  # (the pad channels stay 0)
+            terms = []
+            for img, g_out, w, acc_ in ((img16, g_img, c.clip_weight_16, 1), (img8, g_img8, c.clip_weight_8, 0)):
+                feats, cctx = tower.encode_generated(img, save=True)
+                term, g_f = ops.cos_loss(feats, t32, self._clip_scale)
+                tower.backward(cctx, g_f, g_out, alpha=w, accumulate=acc_)
+                terms.append(term)
+                cctx = None
+            clip16, clip8 = terms
+        elif self.clip_encoder is not None:
             clip16 = clip_loss(img16[..., :3].permute(0, 3, 1, 2), text, self.clip_encoder, images_nhwc=img16)
             clip8 = clip_loss(img8[..., :3].permute(0, 3, 1, 2), text, self.clip_encoder, images_nhwc=img8)
         # KL (t2i_moe_gan.py:846, :1367-1376, :1402-1404)
@@ -325,7 +386,7 @@ class TrainStep:
         if self.pg is not None and step_optim and not accum:
             g_finish = self._bucketed_grad_allreduce(gs, lambda cb: setattr(self.ge, "on_grad_final", cb))
         try:
-            self.ge.backward(ctx, g_img, coef=coef, kl_coef=kl_coef)
+            self.ge.backward(ctx, g_img, coef=coef, kl_coef=kl_coef, g_img8=g_img8)
         finally:
             self.ge.on_grad_final = None
         ops.fold_flush()

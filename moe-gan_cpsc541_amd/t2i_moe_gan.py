@@ -209,12 +209,13 @@ class AuroraGenerator(_FlatModule):
     R x R and ``return_intermediate`` gives the R/2 image)."""
 
     def __init__(self, latent_dim=LATENT_DIM, text_embedding_dim=512, max_resolution=16, num_experts=NUM_EXPERTS,
-                 topk=None, dtype="fp32", seed=0):
+                 topk=None, dtype="fp32", seed=0, clip_grad=False):
         if latent_dim != 512 or text_embedding_dim != 512 or max_resolution not in MAX_RESOLUTIONS:
             raise ValueError("the architecture is fixed at latent 512, text 512 and a 16x16 output (the reference) "
                              f"or one of the progressive resolutions {MAX_RESOLUTIONS[1:]}")
-        super().__init__(generator_shapes(num_experts, max_resolution), frozen=frozen_rgb_prefixes(max_resolution),
-                         dtype=dtype)
+        # clip_grad (train_aurora_gan(clip_grad=True)): the half-resolution to_rgb trains, so it is not frozen
+        super().__init__(generator_shapes(num_experts, max_resolution),
+                         frozen=frozen_rgb_prefixes(max_resolution, clip_grad), dtype=dtype)
         self.latent_dim, self.text_embedding_dim, self.max_resolution = latent_dim, text_embedding_dim, max_resolution
         self.num_experts, self.topk = num_experts, topk
         self._use_checkpointing = False
@@ -346,16 +347,49 @@ def encode_prompt(text, model=None):
     return pooled.float(), tokens.float(), text_len
 
 
-class CLIPLoss(nn.Module):
-    """Reference :66-119 -- forward-only, no gradient (the image branch runs under no_grad)."""
+class _ClipLossFn(torch.autograd.Function):
+    """1 - mean cos(CLIP(image), text) with d loss / d image through the build's frozen image tower
+    (moegan_mi/clip_vit.py encode_generated(save=True) / backward); images NCHW [B, 3, R, R], text [B, 512]."""
 
-    def __init__(self, device=DEVICE):
+    @staticmethod
+    def forward(ctx, images, text, tower):
+        from moegan_mi import ops
+        B, _, R, _ = images.shape
+        nhwc = torch.zeros(B, R, R, 8, device=images.device, dtype=torch.float32)
+        nhwc[..., :3] = images.detach().float().permute(0, 2, 3, 1)
+        feats, tctx = tower.encode_generated(nhwc, save=True)
+        one = torch.ones(1, device=images.device)
+        loss, g_f = ops.cos_loss(feats, text.detach().float().contiguous(), one)
+        ctx.tower, ctx.tctx, ctx.g_f, ctx.nhwc, ctx.in_dtype = tower, tctx, g_f, nhwc, images.dtype
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        g_img = torch.zeros_like(ctx.nhwc)
+        ctx.tower.backward(ctx.tctx, ctx.g_f, g_img)
+        return (g_img[..., :3].permute(0, 3, 1, 2) * g).to(ctx.in_dtype), None, None
+
+
+class CLIPLoss(nn.Module):
+    """Reference :66-119 -- forward-only, no gradient (the image branch runs under no_grad).
+    ``differentiable=True`` (this build's extension): ``loss.backward()`` reaches the image through the registered
+    image tower's own backward; it needs the build's tower (load_clip_weights), not a foreign CLIP model."""
+
+    def __init__(self, device=DEVICE, differentiable=False):
         super().__init__()
         self.device = device
+        self.differentiable = bool(differentiable)
 
     def forward(self, images, text_embeddings):
         if images is None or _clip_model is None:
             return torch.tensor(0.0, device=self.device)
+        if self.differentiable:
+            from moegan_mi.step import clip_tower
+            tower = clip_tower(_clip_model)
+            if tower is None:
+                raise RuntimeError("CLIPLoss(differentiable=True) needs the build's image tower "
+                                   "(t2i_moe_gan.load_clip_weights); the registered model has no backward")
+            return _ClipLossFn.apply(images, text_embeddings, tower)
         with torch.no_grad():
             im = torch.clamp(images, -1, 1)
             if im.shape[-1] != 224 or im.shape[-2] != 224:
@@ -535,7 +569,7 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
                      gradient_accumulation_steps=8, checkpoint_activation=True, batch_memory_limit=20.0,
                      max_resolution=16, *, clip_weight_64=None, clip_weight_32=None, num_experts=NUM_EXPERTS,
                      topk=None, dtype=None, process_group=None, seed=0, resume_from=None, save_every_epoch=False,
-                     use_graphs=True, on_batch_done=None, text_tokens=False, max_text_tokens=None):
+                     use_graphs=True, on_batch_done=None, text_tokens=False, max_text_tokens=None, clip_grad=False):
     """Reference :1029-1669.  ``clip_weight_64``/``clip_weight_32`` (the names train_model.py passes,
     SURVEY.md §0) map to the 16x16 / 8x8 CLIP weights.  ``use_amp`` selects bf16 (the MI355X mixed
     precision; the reference's fp16 GradScaler is not needed) unless ``dtype`` is given.
@@ -557,6 +591,9 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
     rows, through the same captured step; validation feeds the same rows to the generator module.
     ``max_text_tokens``: the caption length the loaders were built with (ProcessedTokenDataset truncates); a
     batch whose key bucket exceeds it is an error.
+    ``clip_grad``: the two CLIP terms carry their gradient into the generator (StepConfig.clip_grad; this build's
+    extension, the reference's terms are gradient-free): needs the build's image tower registered
+    (load_clip_weights); to_rgb_8 then trains and its AdamW state is part of the resume checkpoint.
     ``resume_from``: a resume checkpoint (:1484-1491 layout, ours or the reference's) to start from;
     ``save_every_epoch``: write that layout after every epoch (the reference's commented-out :1642-1652).
 
@@ -580,17 +617,19 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
         import torch.distributed as dist
         rank, world = dist.get_rank(process_group), dist.get_world_size(process_group)
     # max_resolution 16 is the reference generator; 32 / 64 / 128 train the progressive extension (layout.py)
+    if clip_grad and _clip_model is None:
+        raise RuntimeError("clip_grad=True needs the CLIP image tower: call load_clip_weights(path) first")
     generator = AuroraGenerator(num_experts=num_experts, topk=topk, dtype=dtype, seed=seed,
-                                max_resolution=max_resolution).to(device)
+                                max_resolution=max_resolution, clip_grad=clip_grad).to(device)
     discriminator = AuroraDiscriminator(dtype=dtype, seed=seed + 1).to(device)
     if checkpoint_activation:
         generator.enable_checkpointing()
     cfg = StepConfig(E=num_experts, topk=topk, dtype=dtype, r1_gamma=r1_gamma, clip_weight_16=clip_weight_16,
                      clip_weight_8=clip_weight_8, balance_weight=balance_weight, beta1=beta1, beta2=beta2,
-                     max_res=max_resolution)
-    ts = TrainStep(cfg, device, process_group=process_group, gstore=generator._store, dstore=discriminator._store)
-    if _clip_model is not None:  # CLIP terms of the generator loss (logging / guard only: no gradient, :98-101)
-        ts.clip_encoder = _clip_model.encode_image
+                     max_res=max_resolution, clip_grad=clip_grad)
+    # CLIP terms of the generator loss (logging / guard only unless clip_grad: no gradient, :98-101)
+    ts = TrainStep(cfg, device, process_group=process_group, gstore=generator._store, dstore=discriminator._store,
+                   clip_encoder=_clip_model.encode_image if _clip_model is not None else None)
     if rank == 0:
         print(f"Generator parameters: {generator._store.n_opt + (generator._store.total - generator._store.n_opt):,}")
     lrs = _lr_schedule(lr, num_epochs, lr_warmup_epochs)

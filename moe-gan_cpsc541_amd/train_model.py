@@ -87,7 +87,10 @@ def parse_args(argv=None):
     p.add_argument("--max_resolution", type=int, default=16, choices=[16, 32, 64, 128],
                    help="generator output size: 16 = the reference; 32/64/128 = the progressive extension")
     p.add_argument("--clip_weights", type=str, default=None,
-                   help="local OpenAI CLIP state_dict / safetensors: enables the (gradient-free) CLIP loss terms")
+                   help="local OpenAI CLIP state_dict / safetensors: enables the CLIP loss terms (logged only, "
+                        "as in the reference, unless --clip_grad)")
+    p.add_argument("--clip_grad", action="store_true",
+                   help="the CLIP terms train the generator (image-tower backward); needs --clip_weights")
     p.add_argument("--hyperparameters", type=str, default=None,
                    help="SageMaker-style hyperparameters.json (string values, sagemaker_train.py:85-102); batch_size "
                         "and the train_aurora_gan keys override the flags above, other keys are reported as unused")
@@ -96,7 +99,10 @@ def parse_args(argv=None):
                         "*_text_len.npy (encode_captions --tokens) beside each *_text_embeddings.npy")
     p.add_argument("--max_text_tokens", type=int, default=None,
                    help="with --text_tokens: keep each caption's first N token rows only")
-    return p.parse_args(argv)
+    args = p.parse_args(argv)
+    if args.clip_grad and not args.clip_weights:
+        p.error("--clip_grad needs --clip_weights (the CLIP image tower whose backward it runs)")
+    return args
 
 
 def main(argv=None):
@@ -169,6 +175,8 @@ def main(argv=None):
     kw.setdefault("max_resolution", args.max_resolution)
     if args.text_tokens:
         kw.update(text_tokens=True, max_text_tokens=args.max_text_tokens)
+    if args.clip_grad:
+        kw.update(clip_grad=True)
     G, D = M.train_aurora_gan(train_dl, val_dataloader=val_dl, device=device, save_dir=args.save_dir,
                               num_experts=args.num_experts, topk=args.topk, dtype=args.dtype, process_group=pg,
                               resume_from=args.resume, save_every_epoch=args.save_every_epoch, **kw)
