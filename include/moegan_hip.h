@@ -615,6 +615,11 @@ int mg_adamw_dev(float* p, const float* g, float* m, float* v, int64_t n, float 
 /* Same update (t2i_moe_gan.py:1333-1421), 16-B vectors, and (shadow_bf16 != NULL) the bf16 compute copy of the
    updated parameters written in the same pass (replaces the next step's fp32 -> bf16 parameter cast). */
 int mg_adamw_dev_shadow(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, const int32_t* step, const float* sumsq, float max_norm, void* shadow_bf16, const int32_t* flags, int32_t skip_mask, const int32_t* win, int32_t run_mask, void* stream);
+/* mg_adamw_dev_shadow plus, in the same launch and under the same gate, the exponential moving average of the
+   updated parameters: ema = p + beta (ema - p), beta = 2^(-1 / h), h = ema_halflife (> 0, in optimizer steps), and
+   when ema_rampup > 0, h = min(ema_halflife, ema_rampup * step[0]) (StyleGAN's ramp).  p, m, v and the shadow are
+   those of mg_adamw_dev_shadow bit for bit; ema (16-B aligned, length n) is untouched when the gate is closed. */
+int mg_adamw_dev_ema(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1, float beta2, float eps, float weight_decay, const int32_t* step, const float* sumsq, float max_norm, void* shadow_bf16, const int32_t* flags, int32_t skip_mask, const int32_t* win, int32_t run_mask, float* ema, float ema_halflife, float ema_rampup, void* stream);
 
 /* ---- loss guards (t2i_moe_gan.py:1315-1320 NaN/Inf d_loss -> skip the batch; :1367-1376 NaN KL -> 0;
    :1396-1399 NaN/Inf g_loss -> 0) as device-side flags, read by the gated optimizer calls above ---- */

@@ -406,16 +406,29 @@ MG_DEV void st_s(V* q, V x) {
   else *q = x;
 }
 
+// One element of the generator's exponential moving average against the freshly updated parameter,
+// e <- p + beta (e - p), spelled out like adamw_elem (a sub, a mul, an add: no contraction).
+MG_DEV float ema_elem(float ei, float pi, float beta) {
+#pragma clang fp contract(off)
+  const float d = ei - pi;
+  const float bd = beta * d;
+  return pi + bd;
+}
+
 // NT: the optimizer state and gradients stream through non-temporal (cache-streaming) vector loads / stores:
 // every byte is touched once per step, so keeping them out of L2 / MALL leaves those to the parameters' next users
-template <bool NT>
+// EMA: the same launch also advances ``ema`` (one more stream loaded and stored like m and v) towards the new
+// parameters while they are in registers, under the same gate; beta = 2^(-1 / min(halflife, rampup * t)) from the
+// device step counter, so a replayed graph ramps with it.  Without EMA the three extra arguments are unused.
+template <bool NT, bool EMA>
 __global__ __launch_bounds__(256) void k_adamw_dev_v(float* __restrict__ p, const float* __restrict__ g,
                                                      float* __restrict__ m, float* __restrict__ v, int64_t n,
                                                      float lr, float b1, float b2, float eps, float wd,
                                                      const int32_t* __restrict__ step,
                                                      const float* __restrict__ sumsq, float max_norm,
                                                      bf16_t* __restrict__ shadow, const int32_t* flags,
-                                                     int32_t skip_mask, const int32_t* win, int32_t run_mask) {
+                                                     int32_t skip_mask, const int32_t* win, int32_t run_mask,
+                                                     float* __restrict__ ema, float ema_halflife, float ema_rampup) {
   if (!opt_runs(flags, skip_mask, win, run_mask)) return;
   const float t = (float)step[0];
   const float bc1 = 1.f - powf(b1, t);
@@ -426,6 +439,12 @@ __global__ __launch_bounds__(256) void k_adamw_dev_v(float* __restrict__ p, cons
     coef = fminf(max_norm / (tn + 1e-6f), 1.f);
   }
   const float step_size = lr / bc1;
+  float ema_beta = 0.f;
+  if constexpr (EMA) {
+    float h = ema_halflife;
+    if (ema_rampup > 0.f) h = fminf(h, ema_rampup * t);
+    ema_beta = exp2f(-1.f / h);
+  }
   auto upd = [&](float gi, float& pi, float& mi, float& vi) {
     adamw_elem(gi, pi, mi, vi, coef, lr, b1, b2, eps, wd, step_size, bc2_sqrt);
   };
@@ -433,7 +452,7 @@ __global__ __launch_bounds__(256) void k_adamw_dev_v(float* __restrict__ p, cons
   // two 4-parameter vectors per thread and iteration, all eight 16-B loads issued before the math (one vector per
   // iteration left one set of loads in flight per thread: ~4.2 TB/s on the C5 generator's 95 M parameters)
   const int64_t stride = (int64_t)gridDim.x * blockDim.x;
-  auto upd4 = [&](int64_t i, f32x4_t pv, f32x4_t gv, f32x4_t mv, f32x4_t vv) {
+  auto upd4 = [&](int64_t i, f32x4_t pv, f32x4_t gv, f32x4_t mv, f32x4_t vv, f32x4_t ev) {
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
       float pj = pv[j], mj = mv[j], vj = vv[j];
@@ -441,10 +460,12 @@ __global__ __launch_bounds__(256) void k_adamw_dev_v(float* __restrict__ p, cons
       pv[j] = pj;
       mv[j] = mj;
       vv[j] = vj;
+      if constexpr (EMA) ev[j] = ema_elem(ev[j], pj, ema_beta);
     }
     st_s<NT>(reinterpret_cast<f32x4_t*>(p) + i, pv);
     st_s<NT>(reinterpret_cast<f32x4_t*>(m) + i, mv);
     st_s<NT>(reinterpret_cast<f32x4_t*>(v) + i, vv);
+    if constexpr (EMA) st_s<NT>(reinterpret_cast<f32x4_t*>(ema) + i, ev);
     if (shadow) {
       u16x4_t h;
 #pragma unroll
@@ -456,15 +477,22 @@ __global__ __launch_bounds__(256) void k_adamw_dev_v(float* __restrict__ p, cons
   const f32x4_t* g4 = reinterpret_cast<const f32x4_t*>(g);
   const f32x4_t* m4 = reinterpret_cast<const f32x4_t*>(m);
   const f32x4_t* v4 = reinterpret_cast<const f32x4_t*>(v);
+  const f32x4_t* e4 = reinterpret_cast<const f32x4_t*>(ema);
+  auto lde = [&](int64_t i) {  // the ema vector of index i (none without EMA: no load is issued)
+    if constexpr (EMA) return ld4s<NT>(e4 + i);
+    else return f32x4_t{0.f, 0.f, 0.f, 0.f};
+  };
   int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
   for (; i + stride < n4; i += 2 * stride) {
     const int64_t i2 = i + stride;
     const f32x4_t pa = ld4s<NT>(p4 + i), ga = ld4s<NT>(g4 + i), ma = ld4s<NT>(m4 + i), va = ld4s<NT>(v4 + i);
+    const f32x4_t ea = lde(i);
     const f32x4_t pb = ld4s<NT>(p4 + i2), gb = ld4s<NT>(g4 + i2), mb = ld4s<NT>(m4 + i2), vb = ld4s<NT>(v4 + i2);
-    upd4(i, pa, ga, ma, va);
-    upd4(i2, pb, gb, mb, vb);
+    const f32x4_t eb = lde(i2);
+    upd4(i, pa, ga, ma, va, ea);
+    upd4(i2, pb, gb, mb, vb, eb);
   }
-  if (i < n4) upd4(i, ld4s<NT>(p4 + i), ld4s<NT>(g4 + i), ld4s<NT>(m4 + i), ld4s<NT>(v4 + i));
+  if (i < n4) upd4(i, ld4s<NT>(p4 + i), ld4s<NT>(g4 + i), ld4s<NT>(m4 + i), ld4s<NT>(v4 + i), lde(i));
   for (int64_t i = (n4 << 2) + blockIdx.x * (int64_t)blockDim.x + threadIdx.x; i < n;
        i += (int64_t)gridDim.x * blockDim.x) {
     float pi = p[i], mi = m[i], vi = v[i];
@@ -473,6 +501,7 @@ __global__ __launch_bounds__(256) void k_adamw_dev_v(float* __restrict__ p, cons
     m[i] = mi;
     v[i] = vi;
     if (shadow) shadow[i] = f2bf(pi);
+    if constexpr (EMA) ema[i] = ema_elem(ema[i], pi, ema_beta);
   }
 }
 
@@ -729,14 +758,38 @@ extern "C" int mg_adamw_dev_shadow(float* p, const float* g, float* m, float* v,
              (!shadow_bf16 || (reinterpret_cast<uintptr_t>(shadow_bf16) & 7) == 0), "16-B aligned p/g/m/v, 8-B shadow");
   const dim3 grid(std::max<int64_t>(1, std::min<int64_t>(cdiv(n / 4 + 1, 256), 4096)));
   if (g_mg_tune[MG_TUNE_ADAMW_CACHED] == 1)
-    hipLaunchKernelGGL(k_adamw_dev_v<false>, grid, dim3(256), 0, st, p, g, m, v, n, lr, beta1, beta2, eps,
+    hipLaunchKernelGGL((k_adamw_dev_v<false, false>), grid, dim3(256), 0, st, p, g, m, v, n, lr, beta1, beta2, eps,
                        weight_decay, step, sumsq, max_norm, reinterpret_cast<bf16_t*>(shadow_bf16), flags, skip_mask,
-                       win, run_mask);
+                       win, run_mask, nullptr, 0.f, 0.f);
   else
-    hipLaunchKernelGGL(k_adamw_dev_v<true>, grid, dim3(256), 0, st, p, g, m, v, n, lr, beta1, beta2, eps,
+    hipLaunchKernelGGL((k_adamw_dev_v<true, false>), grid, dim3(256), 0, st, p, g, m, v, n, lr, beta1, beta2, eps,
                        weight_decay, step, sumsq, max_norm, reinterpret_cast<bf16_t*>(shadow_bf16), flags, skip_mask,
-                       win, run_mask);
+                       win, run_mask, nullptr, 0.f, 0.f);
   return mg_check_launch("mg_adamw_dev_shadow");
+}
+
+extern "C" int mg_adamw_dev_ema(float* p, const float* g, float* m, float* v, int64_t n, float lr, float beta1,
+                                float beta2, float eps, float weight_decay, const int32_t* step, const float* sumsq,
+                                float max_norm, void* shadow_bf16, const int32_t* flags, int32_t skip_mask,
+                                const int32_t* win, int32_t run_mask, float* ema, float ema_halflife,
+                                float ema_rampup, void* stream) {
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  MG_REQUIRE(ema, "null ema");
+  MG_REQUIRE(ema_halflife > 0.f && ema_rampup >= 0.f, "ema_halflife must be positive, ema_rampup non-negative");
+  if (n == 0) return MG_OK;
+  MG_REQUIRE(mg_al16(p) && mg_al16(g) && mg_al16(m) && mg_al16(v) && mg_al16(ema) &&
+             (!shadow_bf16 || (reinterpret_cast<uintptr_t>(shadow_bf16) & 7) == 0),
+             "16-B aligned p/g/m/v/ema, 8-B shadow");
+  const dim3 grid(std::max<int64_t>(1, std::min<int64_t>(cdiv(n / 4 + 1, 256), 4096)));
+  if (g_mg_tune[MG_TUNE_ADAMW_CACHED] == 1)
+    hipLaunchKernelGGL((k_adamw_dev_v<false, true>), grid, dim3(256), 0, st, p, g, m, v, n, lr, beta1, beta2, eps,
+                       weight_decay, step, sumsq, max_norm, reinterpret_cast<bf16_t*>(shadow_bf16), flags, skip_mask,
+                       win, run_mask, ema, ema_halflife, ema_rampup);
+  else
+    hipLaunchKernelGGL((k_adamw_dev_v<true, true>), grid, dim3(256), 0, st, p, g, m, v, n, lr, beta1, beta2, eps,
+                       weight_decay, step, sumsq, max_norm, reinterpret_cast<bf16_t*>(shadow_bf16), flags, skip_mask,
+                       win, run_mask, ema, ema_halflife, ema_rampup);
+  return mg_check_launch("mg_adamw_dev_ema");
 }
 
 extern "C" int mg_const_fwd(int dtype, const float* cst, int C, int HW, int B, void* out, void* stream) {

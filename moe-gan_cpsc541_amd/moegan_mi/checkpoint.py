@@ -13,9 +13,13 @@ The flat stores keep the AdamW moments in ``store.m`` / ``store.v`` and the step
 (``step_dev`` for the main range, ``step_dev_kl`` for the routers' KL parameters, see params.py); this module
 converts between that and torch's per-parameter format.  Loading uses ``torch.load(weights_only=True)``.
 """
+import logging
+
 import torch
 
 from .layout import is_buffer
+
+logger = logging.getLogger(__name__)
 
 
 def _param_names(store):
@@ -87,11 +91,15 @@ def save_resume(path, generator, discriminator, epoch, step, lr_g, lr_d, betas=(
     one (``epoch_complete``) stores ``epoch + 1``, as the reference's end-of-epoch file does (:1648), so a tool
     that reads 'epoch' the reference's way resumes at the next epoch.  ``generators``: name -> torch.Generator
     state (or the generator itself) stored as ``rng/<name>``, so a resumed run continues the same z, permutation
-    and router-noise streams (every rank's local stream under data parallelism: ``rng/local<r>``)."""
+    and router-noise streams (every rank's local stream under data parallelism: ``rng/local<r>``).
+    A generator that keeps a moving average (``ParamStore.enable_ema``) adds one key, ``generator_ema``: the
+    averaged weights as a state dict in the reference's names.  Without one the key set is the reference's."""
     ck = {"generator": generator.state_dict(), "discriminator": discriminator.state_dict(),
           "optimizer_g": optimizer_state_dict(generator._store, lr_g, betas),
           "optimizer_d": optimizer_state_dict(discriminator._store, lr_d, betas),
           "epoch": int(epoch) + (1 if epoch_complete else 0), "step": int(step)}
+    if generator._store.ema is not None:  # this build's extension: the averaged generator, in the reference's names
+        ck["generator_ema"] = generator._store.ema_state_dict(cpu=False)
     for name, g in (generators or {}).items():
         ck["rng/" + name] = g.get_state() if hasattr(g, "get_state") else g
     torch.save(ck, path)
@@ -104,15 +112,31 @@ def resume_start_epoch(ck_epoch, ck):
     return int(ck_epoch) + (1 if ck.get("epoch_complete", False) else 0)
 
 
+def _load_ema(store, sd):
+    """The moving average of an EMA-enabled store from a checkpoint's ``generator_ema`` (None: not in the file)."""
+    if store.ema is None:
+        return
+    if sd is not None:
+        store.load_ema_state_dict(sd)
+    else:
+        logger.info("checkpoint has no 'generator_ema': the moving average starts from the loaded weights")
+        with torch.no_grad():
+            store.ema.copy_(store.data)
+
+
 def load_resume(path, generator, discriminator, generators=None):
     """Load a resume checkpoint (ours or the reference's); returns (start epoch, step).  A model-only checkpoint
     ({'generator', 'discriminator'}) or a bare generator state dict loads the weights and returns (0, 0).
-    ``generators``: name -> torch.Generator restored from the checkpoint's ``rng/<name>`` states when present."""
+    ``generators``: name -> torch.Generator restored from the checkpoint's ``rng/<name>`` states when present.
+    A generator that keeps a moving average takes it from ``generator_ema``; from a file without that key the
+    average starts at the loaded weights."""
     ck = torch.load(path, map_location="cpu", weights_only=True)
     if "generator" not in ck:  # bare generator state dict (inference.py:44-49)
         generator.load_state_dict(ck)
+        _load_ema(generator._store, None)
         return 0, 0
     generator.load_state_dict(ck["generator"])
+    _load_ema(generator._store, ck.get("generator_ema"))
     if "discriminator" in ck:
         discriminator.load_state_dict(ck["discriminator"])
     if "optimizer_g" in ck:

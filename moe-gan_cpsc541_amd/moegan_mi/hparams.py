@@ -16,7 +16,7 @@ import json
 # sagemaker_train.py:94-99
 INT_KEYS = ("batch_size", "epochs", "kl_annealing_epochs", "lr_warmup_epochs")
 FLOAT_KEYS = ("learning_rate", "beta1", "beta2", "r1_gamma", "clip_weight_16", "clip_weight_8", "kl_weight",
-              "balance_weight")
+              "balance_weight", "ema_kimg", "ema_rampup")
 # keys of the HPO config that name CLIP weights the training entry point knows under other names
 CLIP_ALIASES = {"clip_weight_64": "clip_weight_16", "clip_weight_32": "clip_weight_8"}
 
@@ -33,6 +33,9 @@ TRAIN_KWARGS = {
     "kl_annealing_epochs": ("kl_annealing_epochs", 5),
     "lr_warmup_epochs": ("lr_warmup_epochs", 3),
     "balance_weight": ("balance_weight", 0.01),
+    # this build's extension (no reference counterpart): the generator's moving average, off unless ema_kimg is set
+    "ema_kimg": ("ema_kimg", None),
+    "ema_rampup": ("ema_rampup", 0.05),
 }
 # fixed by the SageMaker entry point (sagemaker_train.py:287-292)
 TRAIN_FIXED = {"log_interval": 100, "save_interval": 500, "gradient_accumulation_steps": 8,

@@ -595,10 +595,23 @@ def opt_prologue(sumsq_buf, step_dev, gate=None):
 
 
 def adamw_dev(p, g, m, v, lr, beta1, beta2, eps, wd, step_dev, sumsq_buf=None, max_norm=0.0, shadow=None,
-              gate=None):
+              gate=None, ema=None, ema_halflife=None, ema_rampup=None):
     """AdamW with the device step counter and clip coefficient; ``shadow`` (bf16, same length) also receives the
-    updated parameters (mg_adamw_dev_shadow); ``gate`` as in opt_prologue."""
+    updated parameters (mg_adamw_dev_shadow); ``gate`` as in opt_prologue.
+
+    ``ema`` (fp32, same length): the same launch also moves it towards the updated parameters (mg_adamw_dev_ema),
+    ema = p + beta (ema - p) with beta = 2^(-1 / min(ema_halflife, ema_rampup * step)); ``ema_halflife`` in
+    optimizer steps (> 0), ``ema_rampup`` None / 0 = a constant beta."""
     fl, skip, win, run = gate if gate is not None else (None, 0, None, 0)
+    if ema is not None:
+        if ema_halflife is None or not ema_halflife > 0:
+            raise ValueError(f"ema_halflife must be positive, got {ema_halflife}")
+        if ema.numel() != p.numel() or ema.dtype != torch.float32:
+            raise ValueError("ema must be fp32 and as long as the parameters")
+        call("mg_adamw_dev_ema", ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr, beta1, beta2, eps, wd,
+             ptr(step_dev), ptr(sumsq_buf), max_norm, ptr(shadow), ptr(fl), skip, ptr(win), run, ptr(ema),
+             float(ema_halflife), float(ema_rampup or 0.0), S())
+        return
     call("mg_adamw_dev_shadow", ptr(p), ptr(g), ptr(m), ptr(v), p.numel(), lr, beta1, beta2, eps, wd, ptr(step_dev),
          ptr(sumsq_buf), max_norm, ptr(shadow), ptr(fl), skip, ptr(win), run, S())
 

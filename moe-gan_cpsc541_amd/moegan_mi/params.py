@@ -107,6 +107,15 @@ class ParamStore:
         self.shadow = None
         if shadow_dtype is not None and shadow_dtype != torch.float32:
             self.shadow = torch.zeros(self.total, device=self.device, dtype=shadow_dtype)
+        self.ema = None  # exponential moving average of ``data`` (enable_ema(); stepped by mg_adamw_dev_ema)
+
+    def enable_ema(self):
+        """Allocate the moving average of the parameters (fp32, ``total`` long) as a copy of ``data``, frozen tail
+        included: the tail never steps, so there the two stay equal.  A second call keeps the buffer and its
+        contents."""
+        if self.ema is None:
+            self.ema = self.data.detach().clone()
+        return self.ema
 
     @property
     def step_count(self):
@@ -149,6 +158,8 @@ class ParamStore:
             self.step_dev_kl = self.step_dev_kl.to(dev)
             if self.acc is not None:
                 self.acc = self.acc.to(dev)
+            if self.ema is not None:
+                self.ema = self.ema.to(dev)
             self.buffers = OrderedDict((n, b.to(dev)) for n, b in self.buffers.items())
             if self.shadow is not None:
                 self.shadow = torch.zeros(self.total, device=dev, dtype=self.shadow_dtype)
@@ -162,6 +173,12 @@ class ParamStore:
 
     def view(self, name):
         return self._v(self.data, name)
+
+    def ema_view(self, name):
+        """``view`` into the moving average (enable_ema() first)."""
+        if self.ema is None:
+            raise RuntimeError("this parameter store keeps no moving average: call enable_ema() first")
+        return self._v(self.ema, name)
 
     def gview(self, name):
         return self._v(self.grad, name)
@@ -210,6 +227,26 @@ class ParamStore:
             t = self.buffers[n] if is_buffer(n) else self.view(n)
             sd[n] = t.detach().clone().cpu() if cpu else t.detach().clone()
         return sd
+
+    def ema_state_dict(self, cpu=True):
+        """``state_dict`` of the moving average: the averaged parameters under the reference's names, the buffers
+        as they are in the live store."""
+        sd = OrderedDict()
+        for n in self.shapes:
+            t = self.buffers[n] if is_buffer(n) else self.ema_view(n)
+            sd[n] = t.detach().clone().cpu() if cpu else t.detach().clone()
+        return sd
+
+    def load_ema_state_dict(self, sd):
+        """Fill the moving average from a state dict in the reference's names (buffers are not averaged: skipped)."""
+        missing = [n for n in self.shapes if n not in sd and not is_buffer(n)]
+        if missing:
+            raise KeyError(f"generator_ema state_dict mismatch: missing={missing[:5]}")
+        with torch.no_grad():
+            for n in self.shapes:
+                if not is_buffer(n):
+                    dst = self.ema_view(n)
+                    dst.copy_(torch.as_tensor(sd[n]).reshape(dst.shape).to(dst.device, torch.float32))
 
     def load_state_dict(self, sd, strict=True):
         missing = [n for n in self.shapes if n not in sd]

@@ -36,7 +36,7 @@ FAMILIES = {
     "modconv_bwd_io": ("hbm", ("mg_modconv_bwd_in", "mg_modconv_bwd_out", "mg_scale_bc")),
     "r1": ("hbm", ("mg_r1",)),
     "sumsq": ("hbm", ("mg_sumsq", "mg_grad_norm_steps")),
-    "adamw": ("hbm", ("mg_adamw_dev", "mg_adamw_dev_shadow", "mg_adamw")),
+    "adamw": ("hbm", ("mg_adamw_dev", "mg_adamw_dev_shadow", "mg_adamw_dev_ema", "mg_adamw")),
     "bias_colsum": ("hbm", ("mg_colsum", "mg_grouped_colsum", "mg_colsum_batch", "mg_segsum", "mg_const_bwd")),
     "weight_prep": ("hbm", ("mg_pack_conv", "mg_pack_conv_flip", "mg_pack_dgrad_s2", "mg_wsq", "mg_wsq_bwd",
                             "mg_router_reparam", "mg_weight_norm_fwd", "mg_weight_norm_bwd", "mg_weight_norm_batch",
@@ -181,6 +181,8 @@ def work(name, a):
         return 28.0 * a["n"]
     if name == "mg_adamw_dev_shadow":
         return (28.0 + (2 if a["shadow_bf16"] else 0)) * a["n"]
+    if name == "mg_adamw_dev_ema":  # + the average: one fp32 load and one fp32 store per parameter
+        return (36.0 + (2 if a["shadow_bf16"] else 0)) * a["n"]
     if name in ("mg_pack_conv", "mg_pack_conv_flip"):
         K = a["KH"] * a["KW"]
         return a["Cout"] * a["Cin"] * K * 4 + (a["rows"] * a["Cin"] if name == "mg_pack_conv" else

@@ -52,7 +52,8 @@ FD, FG = ops.FLAG_D_BAD, ops.FLAG_G_BAD
 class StepConfig:
     def __init__(self, E=4, topk=None, dtype="fp32", r1_gamma=10.0, clip_weight_16=0.1, clip_weight_8=0.05,
                  balance_weight=0.01, beta1=0.5, beta2=0.999, weight_decay=0.01, eps=1e-8, d_clip=0.7, g_clip=0.8,
-                 psi=0.7, fp8=False, max_res=16, deterministic=None, clip_grad=False):
+                 psi=0.7, fp8=False, max_res=16, deterministic=None, clip_grad=False, ema_halflife=None,
+                 ema_rampup=None):
         self.E, self.topk = E, topk
         # generator output resolution: 16 = the reference; 32 / 64 / 128 = the progressive extension (layout.py)
         self.max_res = max_res
@@ -67,6 +68,12 @@ class StepConfig:
         # the CLIP terms train the generator (needs the build's image tower as TrainStep's clip_encoder); False: the
         # reference's gradient-free terms
         self.clip_grad = bool(clip_grad)
+        # exponential moving average of the generator (this build's extension): half-life in optimizer steps, None =
+        # off (the reference's step); ema_rampup caps the half-life at ema_rampup * step early on (None / 0: constant)
+        if ema_halflife is not None and not ema_halflife > 0:
+            raise ValueError(f"ema_halflife must be positive (optimizer steps), got {ema_halflife}")
+        self.ema_halflife = None if ema_halflife is None else float(ema_halflife)
+        self.ema_rampup = float(ema_rampup) if ema_rampup else 0.0
         # deterministic mode (ops.set_deterministic): None = the MOEGAN_DETERMINISTIC environment switch
         self.deterministic = (os.environ.get("MOEGAN_DETERMINISTIC", "0") == "1") if deterministic is None \
             else bool(deterministic)
@@ -114,6 +121,8 @@ class TrainStep:
             frozen_prefixes=frozen_rgb_prefixes(getattr(cfg, "max_res", 16), getattr(cfg, "clip_grad", False)),
             shadow_dtype=self.cdt)
         self.ds = dstore if dstore is not None else ParamStore(discriminator_shapes(), self.dev)
+        if getattr(cfg, "ema_halflife", None) is not None:
+            self.gs.enable_ema()
         self.ge = GeneratorEngine(self.gs, cfg.E, cfg.topk, self.cdt, fp8=getattr(cfg, "fp8", False))
         self.de = DiscriminatorEngine(self.ds, self.cdt)
         self.pg = process_group
@@ -227,7 +236,12 @@ class TrainStep:
     # ---- optimizer ----
     def _adamw(self, store, grad, lr, max_norm, flags, ranges, grad_scale=1.0):
         """clip_grad_norm_ + AdamW over ``grad[:n_opt]`` (torch semantics, :1333-1337 / :1417-1421).  ``ranges``:
-        [(lo, hi, step counter, window bit)] -- each range is one gated launch with its own step counter."""
+        [(lo, hi, step counter, window bit)] -- each range is one gated launch with its own step counter.
+
+        With ``cfg.ema_halflife`` the generator's launches (the store that has ``ema``) also advance its moving
+        average, each range with its own counter and gate (ops.adamw_dev(ema=)): no further launch, host read or
+        collective.  Under data parallelism every rank holds identical parameters after the all-reduced step and so
+        computes identical averages."""
         n = store.n_opt
         if grad_scale != 1.0:  # (loss / accumulation_steps) of the reference == scaling the summed gradient
             grad[:n].mul_(grad_scale)
@@ -238,8 +252,16 @@ class TrainStep:
                             skip_mask=FD, win=self.win)
         c = self.cfg
         bf16_shadow = store.shadow is not None and store.shadow.dtype == torch.bfloat16
+        halflife = getattr(c, "ema_halflife", None)
+        ema = store.ema if halflife is not None and store is self.gs else None
         for lo, hi, step_dev, wbit in live:
             gate = (flags, FD, self.win, wbit)
+            if ema is not None:
+                ops.adamw_dev(store.data[lo:hi], grad[lo:hi], store.m[lo:hi], store.v[lo:hi], lr, c.beta1, c.beta2,
+                              c.eps, c.weight_decay, step_dev, ss, max_norm,
+                              shadow=store.shadow[lo:hi] if bf16_shadow else None, gate=gate, ema=ema[lo:hi],
+                              ema_halflife=halflife, ema_rampup=c.ema_rampup)
+                continue
             ops.adamw_dev(store.data[lo:hi], grad[lo:hi], store.m[lo:hi], store.v[lo:hi], lr, c.beta1, c.beta2,
                           c.eps, c.weight_decay, step_dev, ss, max_norm,
                           shadow=store.shadow[lo:hi] if bf16_shadow else None, gate=gate)

@@ -220,7 +220,46 @@ class AuroraGenerator(_FlatModule):
         self.num_experts, self.topk = num_experts, topk
         self._use_checkpointing = False
         self._eng = None
+        self._clip_grad = bool(clip_grad)
+        object.__setattr__(self, "_ema_gen", None)
         init_generator(self._store, seed)
+
+    def enable_ema(self):
+        """Keep an exponential moving average of the parameters (ParamStore.enable_ema): TrainStep advances it
+        inside the optimizer launch when StepConfig.ema_halflife is set.  Idempotent."""
+        self._store.enable_ema()
+        return self
+
+    def ema_generator(self):
+        """An eval-mode AuroraGenerator of the same configuration whose flat parameters ARE the moving average
+        (``store.ema``: shared memory, no copy), cached.  Every call re-casts its bf16 shadow -- the optimizer
+        kernel's writes to the average do not bump torch's version counter, so the refresh is forced -- and takes
+        the buffers from the live store.  It owns its engine and scratch, so sampling through it leaves the training
+        state (parameters, gradients, moments, buffers) untouched."""
+        st = self._store
+        if st.ema is None:
+            raise RuntimeError("this generator keeps no moving average: train with ema_kimg / "
+                               "StepConfig(ema_halflife=...) or call enable_ema() first")
+        g = self._ema_gen
+        if g is None or g._store.data.data_ptr() != st.ema.data_ptr() or g._store.device != st.ema.device:
+            if g is None:
+                g = AuroraGenerator(max_resolution=self.max_resolution, num_experts=self.num_experts, topk=self.topk,
+                                    dtype="bf16" if self._cdt == torch.bfloat16 else "fp32",
+                                    clip_grad=self._clip_grad)
+                g.requires_grad_(False)
+            g.flat.data = st.ema  # alias, not a copy
+            g._store.rebind(g.flat.data)
+            object.__setattr__(self, "_ema_gen", g)  # cached, not registered as a sub-module
+        else:
+            g._store.refresh_shadow(force=True)
+        with torch.no_grad():
+            for n, b in st.buffers.items():
+                if g._store.buffers[n].device != b.device:
+                    g._store.buffers[n] = b.detach().clone()
+                else:
+                    g._store.buffers[n].copy_(b)
+        g.eval()
+        return g
 
     def _engine(self):
         if self._eng is None or self._eng.st is not self._store or self._eng.dev != self._store.device:
@@ -569,7 +608,8 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
                      gradient_accumulation_steps=8, checkpoint_activation=True, batch_memory_limit=20.0,
                      max_resolution=16, *, clip_weight_64=None, clip_weight_32=None, num_experts=NUM_EXPERTS,
                      topk=None, dtype=None, process_group=None, seed=0, resume_from=None, save_every_epoch=False,
-                     use_graphs=True, on_batch_done=None, text_tokens=False, max_text_tokens=None, clip_grad=False):
+                     use_graphs=True, on_batch_done=None, text_tokens=False, max_text_tokens=None, clip_grad=False,
+                     ema_kimg=None, ema_rampup=0.05):
     """Reference :1029-1669.  ``clip_weight_64``/``clip_weight_32`` (the names train_model.py passes,
     SURVEY.md §0) map to the 16x16 / 8x8 CLIP weights.  ``use_amp`` selects bf16 (the MI355X mixed
     precision; the reference's fp16 GradScaler is not needed) unless ``dtype`` is given.
@@ -594,6 +634,12 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
     ``clip_grad``: the two CLIP terms carry their gradient into the generator (StepConfig.clip_grad; this build's
     extension, the reference's terms are gradient-free): needs the build's image tower registered
     (load_clip_weights); to_rgb_8 then trains and its AdamW state is part of the resume checkpoint.
+    ``ema_kimg`` (this build's extension; None = off, the reference's loop): keep an exponential moving average of
+    the generator with this half-life in thousands of images (StyleGAN's convention), converted to optimizer steps
+    with images per step = dataloader.batch_size x gradient_accumulation_steps x world; ``ema_rampup`` caps the
+    half-life at that fraction of the optimizer steps taken so far (0 / None: constant).  The average is advanced
+    inside the generator's optimizer launch (StepConfig.ema_halflife), sampled with ``generator.ema_generator()``
+    / ``sample_aurora_gan(use_ema=True)`` and saved as ``generator_ema``; validation stays on the live generator.
     ``resume_from``: a resume checkpoint (:1484-1491 layout, ours or the reference's) to start from;
     ``save_every_epoch``: write that layout after every epoch (the reference's commented-out :1642-1652).
 
@@ -616,6 +662,17 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
     if process_group is not None:
         import torch.distributed as dist
         rank, world = dist.get_rank(process_group), dist.get_world_size(process_group)
+    acc = max(1, int(gradient_accumulation_steps))
+    ema_halflife = None
+    if ema_kimg is not None:
+        ema_kimg = float(ema_kimg)
+        bs = getattr(dataloader, "batch_size", None)
+        if not bs:
+            raise ValueError("ema_kimg converts thousands of images to optimizer steps and needs "
+                             "dataloader.batch_size; this loader has none (a batch_sampler?)")
+        if not ema_kimg > 0:
+            raise ValueError(f"ema_kimg must be positive, got {ema_kimg}")
+        ema_halflife = ema_kimg * 1000.0 / (int(bs) * acc * world)
     # max_resolution 16 is the reference generator; 32 / 64 / 128 train the progressive extension (layout.py)
     if clip_grad and _clip_model is None:
         raise RuntimeError("clip_grad=True needs the CLIP image tower: call load_clip_weights(path) first")
@@ -626,7 +683,8 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
         generator.enable_checkpointing()
     cfg = StepConfig(E=num_experts, topk=topk, dtype=dtype, r1_gamma=r1_gamma, clip_weight_16=clip_weight_16,
                      clip_weight_8=clip_weight_8, balance_weight=balance_weight, beta1=beta1, beta2=beta2,
-                     max_res=max_resolution, clip_grad=clip_grad)
+                     max_res=max_resolution, clip_grad=clip_grad, ema_halflife=ema_halflife,
+                     ema_rampup=float(ema_rampup) if ema_rampup is not None else None)
     # CLIP terms of the generator loss (logging / guard only unless clip_grad: no gradient, :98-101)
     ts = TrainStep(cfg, device, process_group=process_group, gstore=generator._store, dstore=discriminator._store,
                    clip_encoder=_clip_model.encode_image if _clip_model is not None else None)
@@ -634,7 +692,6 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
         print(f"Generator parameters: {generator._store.n_opt + (generator._store.total - generator._store.n_opt):,}")
     lrs = _lr_schedule(lr, num_epochs, lr_warmup_epochs)
     gan_loss = AuroraGANLoss(device)
-    acc = max(1, int(gradient_accumulation_steps))
     # randomness: per-rank z / permutation, rank-shared router noise
     g_local = torch.Generator(device=device).manual_seed(1_000_003 * (seed + 1) + 7919 * rank)
     g_shared = torch.Generator(device=device).manual_seed(1_000_003 * (seed + 1) + 17)
@@ -805,10 +862,14 @@ def _validate(generator, discriminator, loader, gan_loss, temperature_factor, ef
 
 
 def sample_aurora_gan(generator, text_prompt, num_samples=1, truncation_psi=0.7, device=DEVICE, text_tokens=None,
-                      text_len=None, prompt_tokens=False):
+                      text_len=None, prompt_tokens=False, use_ema=False):
     """Reference :1672-1709: eval mode (hard top-1 routing), clamp to [-1, 1].  ``text_tokens`` [B or 1, Lk, 512] /
     ``text_len``: per-token text features for the cross-attention (AuroraGenerator.forward).  ``prompt_tokens``
-    with a string prompt: the prompt's own token features (encode_prompt) feed the cross-attention too."""
+    with a string prompt: the prompt's own token features (encode_prompt) feed the cross-attention too.
+    ``use_ema``: sample the generator's moving average (``generator.ema_generator()``) instead of its live weights;
+    the live generator then keeps its mode."""
+    if use_ema:
+        generator = generator.ema_generator()
     generator.eval()
     z = torch.randn(num_samples, LATENT_DIM, device=device, dtype=torch.float32)
     if isinstance(text_prompt, str) or (isinstance(text_prompt, list) and isinstance(text_prompt[0], str)):

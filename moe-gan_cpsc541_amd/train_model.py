@@ -99,6 +99,11 @@ def parse_args(argv=None):
                         "*_text_len.npy (encode_captions --tokens) beside each *_text_embeddings.npy")
     p.add_argument("--max_text_tokens", type=int, default=None,
                    help="with --text_tokens: keep each caption's first N token rows only")
+    p.add_argument("--ema_kimg", type=float, default=None,
+                   help="keep an exponential moving average of the generator with this half-life, in thousands of "
+                        "images (StyleGAN's convention); saved as 'generator_ema' (default: off)")
+    p.add_argument("--ema_rampup", type=float, default=0.05,
+                   help="with --ema_kimg: cap the half-life at this fraction of the steps taken so far (0: none)")
     args = p.parse_args(argv)
     if args.clip_grad and not args.clip_weights:
         p.error("--clip_grad needs --clip_weights (the CLIP image tower whose backward it runs)")
@@ -177,12 +182,17 @@ def main(argv=None):
         kw.update(text_tokens=True, max_text_tokens=args.max_text_tokens)
     if args.clip_grad:
         kw.update(clip_grad=True)
+    if args.ema_kimg is not None:
+        kw.setdefault("ema_kimg", args.ema_kimg)
+        kw.setdefault("ema_rampup", args.ema_rampup)
     G, D = M.train_aurora_gan(train_dl, val_dataloader=val_dl, device=device, save_dir=args.save_dir,
                               num_experts=args.num_experts, topk=args.topk, dtype=args.dtype, process_group=pg,
                               resume_from=args.resume, save_every_epoch=args.save_every_epoch, **kw)
     if rank == 0:
-        torch.save({"generator": G.state_dict(), "discriminator": D.state_dict()},
-                   os.path.join(args.save_dir, "aurora_final.pt"))
+        final = {"generator": G.state_dict(), "discriminator": D.state_dict()}
+        if G._store.ema is not None:  # the averaged weights, in the reference's names (generate_images.py --ema)
+            final["generator_ema"] = G._store.ema_state_dict(cpu=False)
+        torch.save(final, os.path.join(args.save_dir, "aurora_final.pt"))
         print("Training complete.")
 
 
