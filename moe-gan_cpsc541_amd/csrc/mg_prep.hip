@@ -196,9 +196,28 @@ MG_DEV void wn_fwd_row(const float* __restrict__ v, const float* __restrict__ g,
     float t = 0.f;
     for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += red[i];
     red[0] = sqrtf(t);
+    red[15] = t;
   }
   __syncthreads();
   float n = red[0];
+  if (red[15] < 0x1p-80f) {  // (block-uniform) the squares lie in or under fp32's denormal range and have lost
+    __syncthreads();         // their bits: sum them again scaled by 2^128 (exact), |v| = sqrt(sum) 2^-64
+    s = 0.f;
+    for (int k = threadIdx.x; k < K; k += blockDim.x) {
+      float x = v[(int64_t)o * K + k] * 0x1p64f;
+      s += x * x;
+    }
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+      float t = 0.f;
+      for (int i = 0; i < (int)(blockDim.x >> 6); ++i) t += red[i];
+      red[0] = sqrtf(t) * 0x1p-64f;
+    }
+    __syncthreads();
+    n = red[0];
+  }
   if (threadIdx.x == 0) norm[o] = n;
   float sc = g[o] / n;
   for (int k = threadIdx.x; k < K; k += blockDim.x) W[(int64_t)o * K + k] = v[(int64_t)o * K + k] * sc;
