@@ -92,6 +92,15 @@ typedef struct mg_epilogue {
   int64_t add_ld;
   void* out_pre;       /* optional second output: the value before the activation (same dtype as C) */
   int64_t ld_pre;
+  /* Modulated-conv data gradient with mg_modconv_bwd_in in the epilogue (mg_gemm with a_kc = 1, b_kc = 0 and
+     mg_conv2d_fwd only; gs = NULL: off).  The GEMM's result is gxt [M = B * HW, N = Cin]; with scale = the style
+     rows s (scale_shift = log2 HW, scale_ld = its pitch) the call stores C (+)= gxt * s and adds
+     gs[b * gs_ld + n] += sum over the pixels of image b of gxt * gs_x[m * ld_gs_x + n] (fp32 atomics), gxt never
+     stored (rounded as the plain call's output buffer would round it, so gx has the two calls' bits).  Only shapes mg_modconv_dgrad_fusable admits; any other is an argument error. */
+  float* gs;
+  int64_t gs_ld;
+  const void* gs_x;    /* the conv's saved input x [M, N], in the operands' dtype */
+  int64_t ld_gs_x;
 } mg_epilogue;
 
 const char* mg_last_error(void);
@@ -109,7 +118,7 @@ int mg_workspace_reserve(size_t bytes, void* stream);
 int64_t mg_workspace_bytes(void* stream);
 /* Tuning override for measurements (key: 0 conv-wgrad tile, 1 grouped-wgrad tile, 2 conv tile,
    3 gemm tile [64 | 128], 4 conv-wgrad splits, 5 disable split-K slabs, 6 enable the XCD-aware tile
-   order; value 0 = automatic). */
+   order, 29 keep the modulated conv's gx / gs out of the data gradient's epilogue; value 0 = automatic). */
 int mg_set_tuning(int key, int value);
 
 /* Measurement of one call inside a training step (bench.py's roofline kernel; no reference
@@ -378,6 +387,13 @@ int mg_scale_bc(int dtype, const void* x, int64_t ldx, const float* s, int64_t l
 /* ModulatedConv backward, input side: gx (+)= gxt*s, gs[b,ci] += sum_pix gxt*x (s and gs rows of pitch ld_s:
    column slices of the batched style matrix). */
 int mg_modconv_bwd_in(int gxt_dtype, const void* gxt, int64_t ld_gxt, int dtype, const void* x, int64_t ld_x, const float* s, int64_t ld_s, int B, int HW, int Cin, int gx_dtype, void* gx, int64_t ld_gx, int accumulate, float* gs, void* stream);
+
+/* 1 when the data gradient of this modulated conv (k = 1: mg_gemm of gyt [B*H*W, Cout] with W [Cout, Cin], a_kc = 1,
+   b_kc = 0; k = 3: mg_conv2d_fwd of gyt with the flipped pack) can take mg_epilogue.gs and so replace
+   mg_modconv_bwd_in; 0 when the caller runs the two calls.  0 in deterministic mode and with tuning slot 29 set, for
+   shapes the plain call runs as split-K slabs or through the direct 32-channel conv, H * W < 16 or no power of two,
+   Cin % 8, Cout below one K step (3x3), a bf16 gx from fp32 operands, unaligned s / x / gx. */
+int mg_modconv_dgrad_fusable(int dtype, int gx_dtype, int k, int B, int H, int W, int Cout, int Cin, const float* s, int64_t ld_s, const void* x, int64_t ld_x, const void* gx, int64_t ld_gx);
 
 /* Generator KL total and per-router gradient coefficients (total clamped at 50, t2i_moe_gan.py:1369-1370). */
 int mg_kl_coefs(const float* kl2, int R, float eff_w, float* coef, float* total, void* stream);

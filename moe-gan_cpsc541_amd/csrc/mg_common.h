@@ -170,7 +170,8 @@ enum { MG_TUNE_WGRAD_TILE = 0, MG_TUNE_GWGRAD_TILE = 1, MG_TUNE_CONV_TILE = 2, M
        MG_TUNE_ATOMIC_MINK = 26,     // atomic split-K GEMMs: the least K per split (0: automatic)
        MG_TUNE_WIDE_BLOCKS = 27,     // mg_wgrad_wide.hip grid target (blocks): 0 automatic (256)
        MG_TUNE_WGRAD_SLAB_BLOCKS = 28,  // conv weight-gradient slab split target (blocks): 0 automatic (1024)
-       MG_TUNE_COUNT = 29 };
+       MG_TUNE_MODGRAD_UNFUSED = 29,  // 1: the modulated conv's gx / gs as mg_modconv_bwd_in after the data-gradient GEMM, never in its epilogue (A/B)
+       MG_TUNE_COUNT = 30 };
 extern std::atomic<int> g_mg_tune[MG_TUNE_COUNT];
 // Deterministic mode (mg_set_tuning(MG_TUNE_DETERMINISTIC, 1)): every reduction that crosses workgroups runs in
 // a fixed order -- per-block partial rows in the stream's workspace folded by one pass, or one writer per
@@ -250,6 +251,14 @@ bool mg_conv3_direct(const void* x, int B, int H, int Cin, const void* wpack, in
 bool mg_wgrad3_direct(const void* gy, int64_t ldg, const void* x, int B, int H, int Cin, float** ws_out, int* splits,
                       bool* deferred,
                       hipStream_t st);
+
+// mg_modgrad.hip: the modulated conv's data gradient with gx / gs in the GEMM epilogue (mg_epilogue.gs set).  k = 1:
+// A = gyt [M, K] x B = W [K, N]; k = 3: the implicit 3x3 / s1 / p1 conv of gyt [B, H, W, K / 9] with wflip.  MG_OK when
+// launched, MG_ERR_ARG (mg_last_error says why) for a call mg_modconv_dgrad_fusable does not admit.
+int mg_modgrad_gemm(int dtype, int M, int N, int K, const void* A, int64_t lda, const void* B, int64_t ldb, void* C,
+                    int64_t ldc, int c_dtype, const mg_epilogue* e, hipStream_t st);
+int mg_modgrad_conv(int dtype, const void* x, int B, int H, int W, int Cin, const void* wpack, int Cout, void* y,
+                    int64_t ldy, int y_dtype, const mg_epilogue* e, hipStream_t st);
 
 // mg_wgrad_wide.hip: wide split-K weight gradients (bf16 [K][M] x [K][N] -> fp32 C +=), true when handled
 bool mg_wgrad_wide(int M, int N, int K, const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t ldc,

@@ -723,6 +723,44 @@ struct EpiQuickGeluGrad : Epi<TO> {
   }
 };
 
+// Modulated-conv data gradient with the input side of its backward in the epilogue: the GEMM's result is gxt
+// (mg_modconv.hip), the tile stores gx (+)= gxt * s through Epi's own per-image column scale (scale / scale_shift /
+// scale_ld, HW = 1 << scale_shift pixels per image) and adds gs[b, c] += sum over the tile's rows of image b of
+// gxt * x, with gxt still in fp32 -- mg_modconv_bwd_in's two passes over gxt and its pass over x become one read of
+// x.  epi_tile forms the products in each wave's 16-row staging band, sums the band's columns there and carries
+// the sums in registers over the wave tile's bands; a 16-row band lies inside one image (HW >= 16, a power of two),
+// and one fp32 atomic per (image, column) leaves the wave tile.  An epilogue type of its own for EpiQuickGeluGrad's
+// reason; kColSum compiles the band sums into these kernels only.  The host admits alpha = 1 and no other epilogue
+// step, and launches only with vec_ok (mg_modgrad.hip).
+template <typename TO, typename TX>
+struct EpiModGrad : Epi<TO> {
+  typedef Epi<TO> Base;
+  static constexpr bool kColSum = true;
+  float* gs; int64_t gs_ld;         // style gradient rows [B, .] (a column slice: only columns n < N are touched)
+  const TX* gs_x; int64_t ld_gs_x;  // the conv's saved input x [M, N]
+  bool host_vec_ok() const {
+    return Base::host_vec_ok() && this->scale && (reinterpret_cast<uintptr_t>(gs_x) & 15) == 0 && ld_gs_x % 8 == 0;
+  }
+  // 1: gxt first takes the bf16 rounding that the two-kernel path's gxt buffer gives it, so gx has that path's
+  // bits and gs differs from it by summation order only (the same tile and K loop form the same fp32 gxt)
+  int round_gxt;
+  // p[j] = v[j] * x[m, n + j] for 8 columns n .. n + 7 < N (v rounded in place first when round_gxt)
+  MG_DEV void xprod8(int m, int n, float* v, float* p) const {
+    if (round_gxt) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) v[j] = bf2f(f2bf(v[j]));
+    }
+    float t[8];
+    ld8(gs_x + (int64_t)m * ld_gs_x + n, t);
+#pragma unroll
+    for (int j = 0; j < 8; ++j) p[j] = v[j] * t[j];
+  }
+  MG_DEV int image(int m) const { return m >> this->scale_shift; }
+  MG_DEV void gs_add(int b, int n, float v) const { atomicAdd(gs + (int64_t)b * gs_ld + n, v); }
+};
+template <class EP, class = void> struct has_colsum : std::false_type {};
+template <class EP> struct has_colsum<EP, std::void_t<decltype(EP::kColSum)>> : std::integral_constant<bool, EP::kColSum> {};
+
 // grouping descriptor (device tables)
 struct Grouping {
   int mode;              // 0 none, 1 grouped-M (rows), 2 grouped-K (reduction rows)
@@ -850,6 +888,24 @@ MG_DEV void epi_tile(const f32x4_t (&acc)[BM / 32][BN / 32], void* smem, const E
         if (e < 2 * WN && m < Mloc && n + 8 <= N) ep.pf_load(mrow_base + m, n, pf[i][t]);
       }
   }
+  // kColSum epilogues (EpiModGrad): per-image column sums of v * x, carried over the wave tile's bands; lane
+  // (+ 64 t) owns column lane + 64 t of the wave's WN
+  constexpr bool CSUM = has_colsum<EP>::value;
+  constexpr int NCS = CSUM ? (WN + 63) / 64 : 1;
+  float csum[NCS];
+  int cs_img = -1;  // the image the sums belong to (none yet)
+  auto cs_flush = [&]() {
+    if constexpr (CSUM) {
+#pragma unroll
+      for (int t = 0; t < NCS; ++t) {
+        const int c = lane + 64 * t, n = n0 + wn * WN + c;
+        if (c < WN && n < N) ep.gs_add(cs_img, n, csum[t]);
+      }
+    }
+  };
+  (void)csum;
+  (void)cs_img;
+  (void)cs_flush;
   // each wave stages through its own LDS band: one block barrier retires the K loop's reads of the
   // tiles, after that a wave only orders its own LDS writes and reads (wave-scope fence)
   __syncthreads();
@@ -895,9 +951,39 @@ MG_DEV void epi_tile(const f32x4_t (&acc)[BM / 32][BN / 32], void* smem, const E
           f32x4_t a = *reinterpret_cast<const f32x4_t*>(src), b = *reinterpret_cast<const f32x4_t*>(src + 4);
 #pragma unroll
           for (int j = 0; j < 4; ++j) { v[j] = a[j]; v[j + 4] = b[j]; }
+          if constexpr (CSUM) {  // the lane's 8 staged values become their products with x, in place
+            float p[8];
+            ep.xprod8(mrow_base + m, n, v, p);
+            float* dst = cs + rr * CSP + cc;
+            *reinterpret_cast<f32x4_t*>(dst) = f32x4_t{p[0], p[1], p[2], p[3]};
+            *reinterpret_cast<f32x4_t*>(dst + 4) = f32x4_t{p[4], p[5], p[6], p[7]};
+          }
           ep.vec8(mrow_base + m, n, v);
         } else {
           for (int j = 0; j < 8 && n + j < N; ++j) ep(mrow_base + m, n + j, src[j]);
+        }
+      }
+      if constexpr (CSUM) {
+        __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+        __builtin_amdgcn_wave_barrier();
+        if (mb < Mloc) {  // (wave-uniform) rows mb .. mb + nr - 1 of one image hold products; N % 8 == 0 (host)
+          const int img = ep.image(mrow_base + mb), nr = min(16, Mloc - mb);
+          if (img != cs_img) {
+            if (cs_img >= 0) cs_flush();
+            cs_img = img;
+#pragma unroll
+            for (int t = 0; t < NCS; ++t) csum[t] = 0.f;
+          }
+#pragma unroll
+          for (int t = 0; t < NCS; ++t) {
+            const int c = lane + 64 * t;
+            if (c < WN && nb + c < N) {
+              float s = 0.f;
+#pragma unroll
+              for (int rr = 0; rr < 16; ++rr) s += rr < nr ? cs[rr * CSP + c] : 0.f;
+              csum[t] += s;
+            }
+          }
         }
       }
     } else {
@@ -908,6 +994,9 @@ MG_DEV void epi_tile(const f32x4_t (&acc)[BM / 32][BN / 32], void* smem, const E
         if (m < Mloc && n < N) ep(mrow_base + m, n, cs[rr * CSP + cc]);
       }
     }
+  }
+  if constexpr (CSUM) {
+    if (cs_img >= 0) cs_flush();  // the wave tile's last image
   }
 }
 

@@ -198,6 +198,10 @@ extern "C" int mg_gemm(int dtype, int M, int N, int K, const void* A, int64_t ld
   MG_REQUIRE(under2g((a_kc ? (int64_t)M : K) * lda, dtype) && under2g((b_kc ? (int64_t)N : K) * ldb, dtype) &&
                  under2g((int64_t)M * ldc, c_dtype),
              "an operand exceeds 2 GiB (32-bit buffer offsets)");
+  if (ep && ep->gs) {  // a modulated conv's 1x1 data gradient with gx / gs in the epilogue (mg_modgrad.hip)
+    MG_REQUIRE(a_kc && !b_kc && !x3 && splits <= 1, "mg_epilogue.gs: gyt [M, K] x W [K, N], bf16 or fp32, no split-K");
+    return mg_modgrad_gemm(dtype, M, N, K, A, lda, B, ldb, C, ldc, c_dtype, ep, reinterpret_cast<hipStream_t>(stream));
+  }
   if (splits < 1 && dtype == MG_BF16 && !x3 && !a_kc && !b_kc && c_dtype == MG_F32 && ep && ep->atomic &&
       !ep->bias && !ep->scale && !ep->rowscale && !ep->act && !ep->aux && !ep->resid && !ep->accumulate &&
       !ep->remap_taps && !ep->a_idx && !ep->a_rowscale && !ep->a_gelu && !ep->addvec && !ep->out_pre &&
@@ -526,6 +530,10 @@ extern "C" int mg_conv2d_fwd(int dtype, const void* x, int B, int H, int W, int 
              "an operand exceeds 2 GiB (32-bit buffer offsets)");
   if (B == 0) return MG_OK;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (ep && ep->gs) {  // a modulated conv's 3x3 data gradient with gx / gs in the epilogue (mg_modgrad.hip)
+    MG_REQUIRE(KH == 3 && KW == 3 && stride == 1 && pad == 1 && !in_scale, "mg_epilogue.gs: 3x3 / stride 1 / pad 1, no in_scale");
+    return mg_modgrad_conv(dtype, x, B, H, W, Cin, wpack, Cout, y, ldy, y_dtype, ep, st);
+  }
   if (dtype == MG_F32) {
     if (y_dtype == MG_F32) run_conv_tiles<float, float>(x, B, H, W, Cin, wpack, Cout, KH, KW, stride, pad, in_scale, y, ldy, ep, st);
     else run_conv_tiles<float, bf16_t>(x, B, H, W, Cin, wpack, Cout, KH, KW, stride, pad, in_scale, y, ldy, ep, st);

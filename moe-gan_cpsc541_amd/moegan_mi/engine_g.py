@@ -231,23 +231,21 @@ class GeneratorEngine:
         gdd = torch.empty(B, rows, device=self.dev, dtype=torch.float32)
         ops.modconv_bwd_out(gz.view(P, -1), z.view(P, -1), d, B, HW, rows, act, gyt, gdd,
                             zsub=None if zsub is None else zsub.view(P, -1))
-        # data gradient of the shared-weight conv
-        if k == 3 and "wflipq" in pk:  # MX-fp8 data gradient (gradient rows quantized per 32 channels)
-            gq, gsc = ops.quant_mx8(gyt)
-            gxt = ops.conv2d_mx8(gq.view(B, H, W, rows), gsc, *pk["wflipq"], Cin, 3, 3, 1, 1, out_dtype=self.cdt)
-        elif k == 3:
-            gxt = ops.conv2d(gyt.view(B, H, W, rows), pk["wflip"], Cin, 3, 3, 1, 1,
-                             out_dtype=torch.float32 if gx_f32 else None)
-        else:
-            gxt = ops.gemm(gyt, pk["w"], P, Cin, rows, b_kc=False)
         batched = self._GS is not None and pre in self.style_cols
         if batched:
             c = self.style_cols[pre]
             gs = self._GS[:, c:c + Cin]
         else:
             gs = ops.zeros(B, Cin, device=self.dev)
-        ops.modconv_bwd_in(gxt.view(P, Cin), x.view(P, Cin), s, B, HW, Cin,
-                           None if gx is None else gx.view(P, -1), gs, accumulate)
+        # data gradient of the shared-weight conv, gxt; then gx (+)= gxt * s and gs += sum_pix gxt * x
+        gx2 = None if gx is None else gx.view(P, -1)
+        if k == 3 and "wflipq" in pk:  # MX-fp8 data gradient (gradient rows quantized per 32 channels)
+            gq, gsc = ops.quant_mx8(gyt)
+            gxt = ops.conv2d_mx8(gq.view(B, H, W, rows), gsc, *pk["wflipq"], Cin, 3, 3, 1, 1, out_dtype=self.cdt)
+            ops.modconv_bwd_in(gxt.view(P, Cin), x.view(P, Cin), s, B, HW, Cin, gx2, gs, accumulate)
+        else:  # both in the data gradient's epilogue where the library covers the shape: no gxt buffer, x read once
+            ops.modconv_bwd_data(gyt, pk["wflip"] if k == 3 else pk["w"], k, B, H, W, Cin, x.view(P, Cin), s, gx2, gs,
+                                 accumulate, gxt_f32=gx_f32)
         # weight gradient (fp32, reference layout), on the side stream
         gW = self.G(pre + "weight")
         if rows == Cout:

@@ -720,9 +720,54 @@ def scale_bc(x, s, out=None):
 def modconv_bwd_in(gxt, x, s, B, HW, Cin, gx, gs, accumulate=0):
     """gx (+)= gxt * s; gs += sum_pix gxt * x.  s / gs may be column slices sharing one row pitch."""
     assert s.stride(0) == gs.stride(0) and s.stride(-1) == 1 and gs.stride(-1) == 1
-    call("mg_modconv_bwd_in", dt(gxt), ptr(gxt), gxt.shape[-1], dt(x), ptr(x), x.shape[-1], ptr(s), s.stride(0), B, HW,
-         Cin, dt(gx) if gx is not None else 0, ptr(gx), gx.shape[-1] if gx is not None else 0, accumulate, ptr(gs),
+    call("mg_modconv_bwd_in", dt(gxt), ptr(gxt), gxt.stride(0), dt(x), ptr(x), x.stride(0), ptr(s), s.stride(0), B, HW,
+         Cin, dt(gx) if gx is not None else 0, ptr(gx), gx.stride(0) if gx is not None else 0, accumulate, ptr(gs),
          S())
+
+
+TUNE_MODGRAD_UNFUSED = 29  # mg_common.h MG_TUNE_MODGRAD_UNFUSED: 1 keeps gx / gs out of the data gradient's epilogue
+
+
+def modconv_dgrad_fusable(gyt, k, B, H, W, Cin, x, s, gx):
+    """Whether modconv_dgrad may replace the data-gradient GEMM + modconv_bwd_in pair for this modulated conv
+    (mg_modconv_dgrad_fusable: the library's own answer, so caller and entry point cannot disagree).  gyt [B*H*W,
+    rows]; x [..., Cin]; s [B, Cin] (a column slice); gx [B*H*W, >= Cin] or None (style gradient only: not fused)."""
+    if gx is None:
+        return False
+    return bool(L.lib().mg_modconv_dgrad_fusable(_gdt(gyt), dt(gx), k, B, H, W, gyt.shape[-1], Cin, ptr(s),
+                                                 s.stride(0), ptr(x), x.stride(0), ptr(gx), gx.stride(0)))
+
+
+def modconv_dgrad(gyt, w, k, B, H, W, Cin, x, s, gx, gs, accumulate=0):
+    """The modulated conv's data gradient with its input side in the GEMM epilogue: gxt = conv^T(gyt, w) stays in
+    the accumulators, gx (+)= gxt * s, gs += sum_pix gxt * x (fp32 atomics).  gyt [B*H*W, rows] contiguous; w: the
+    flipped 3x3 pack (k = 3) or the [rows, Cin] weight (k = 1); x, gx: [B*H*W, Cin] rows (any pitch).  Only where
+    modconv_dgrad_fusable says so; anything else raises."""
+    rows = gyt.shape[-1]
+    ep = E(scale=s, scale_shift=ilog2(H * W), scale_ld=s.stride(0), accumulate=accumulate, gs=gs,
+           gs_ld=gs.stride(0), gs_x=x, ld_gs_x=x.stride(0))
+    if k == 3:
+        call("mg_conv2d_fwd", dt(gyt), ptr(gyt), B, H, W, rows, ptr(w), Cin, 3, 3, 1, 1, None, ptr(gx),
+             gx.stride(0), dt(gx), ep, S())
+    else:
+        call("mg_gemm", _gdt(gyt), B * H * W, Cin, rows, ptr(gyt), rows, 1, ptr(w), _ld(w), 0, ptr(gx),
+             gx.stride(0), dt(gx), ep, 1, S())
+
+
+def modconv_bwd_data(gyt, w, k, B, H, W, Cin, x, s, gx, gs, accumulate=0, gxt_f32=False):
+    """The input side of a modulated conv's backward from gyt: gx (+)= conv^T(gyt, w) * s and gs += sum_pix
+    conv^T(gyt, w) * x.  One launch (modconv_dgrad) where the library covers the shape, else the data gradient into
+    a gxt buffer (fp32 if ``gxt_f32``) followed by modconv_bwd_in.  Returns True when it ran fused."""
+    if modconv_dgrad_fusable(gyt, k, B, H, W, Cin, x, s, gx):
+        modconv_dgrad(gyt, w, k, B, H, W, Cin, x, s, gx, gs, accumulate)
+        return True
+    P, rows = B * H * W, gyt.shape[-1]
+    if k == 3:
+        gxt = conv2d(gyt.view(B, H, W, rows), w, Cin, 3, 3, 1, 1, out_dtype=torch.float32 if gxt_f32 else None)
+    else:
+        gxt = gemm(gyt, w, P, Cin, rows, b_kc=False)
+    modconv_bwd_in(gxt.view(P, Cin), x, s, B, H * W, Cin, gx, gs, accumulate)
+    return False
 
 
 # ---------------------------------------------------------------------------

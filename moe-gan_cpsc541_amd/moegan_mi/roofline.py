@@ -166,6 +166,9 @@ def work(name, a):
     if name == "mg_scale_bc":
         return 2.0 * a["B"] * a["HW"] * a["C"] * ELT[a["dtype"]]
     if name == "mg_modconv_bwd_in":
+        # (only the data gradients the GEMM epilogue does not cover still make this call -- ops.modconv_bwd_data; a
+        # covered one is one mg_gemm / mg_conv2d_fwd call, priced by its FLOPs in the MFMA families: its epilogue's
+        # read of x and store of gx replace this call's three passes and the GEMM's own store of gxt)
         n = a["B"] * a["HW"] * a["Cin"]
         gx = ELT[a["gx_dtype"]] * (2 if a["accumulate"] else 1)
         return n * (ELT[a["gxt_dtype"]] + ELT[a["dtype"]] + gx)
