@@ -273,13 +273,16 @@ int mg_clip_patches_bwd(int g_dtype, const void* g_patches, int img_dtype, const
    g_f = -(scale[0] / B) (t^ - cos f^) / |f| (zero rows where the similarity is not finite); scale is a device scalar. */
 int mg_cos_loss(const float* f, const float* text, int B, int C, const float* scale, float* loss, float* g_f, void* stream);
 
-/* LayerNorm over C (128/256/512) per row (+ optional LeakyReLU), saving mean/rstd. t2i_moe_gan.py:505-507, :684. */
+/* LayerNorm over C (128/256/512/768) per row (+ optional LeakyReLU), saving mean/rstd. t2i_moe_gan.py:505-507, :684. */
 int mg_layernorm_fwd(int dtype, const void* x, int64_t ldx, int R, int C, const float* gamma, const float* beta, float eps, void* y, int64_t ldy, float* mean, float* rstd, int act, void* stream);
 
 /* LayerNorm backward (gx (+)=, ggamma/gbeta += via atomics).  C = 768 (the CLIP tower): gx only, ggamma = gbeta = NULL. */
 int mg_layernorm_bwd(int dtype, int gy_dtype, const void* gy, int64_t ldg, const void* x, int64_t ldx, int R, int C, const float* mean, const float* rstd, const float* gamma, void* gx, int64_t ldgx, int accumulate, float* ggamma, float* gbeta, void* stream);
 
-/* Self-attention core for nn.MultiheadAttention (8 heads) on packed qkv [B*L, 3C]; saves logsumexp. t2i_moe_gan.py:513, :546. */
+/* Self-attention core for nn.MultiheadAttention (8 heads) on packed qkv [B*L, 3C]; saves logsumexp. t2i_moe_gan.py:513, :546.
+   Head dim C / heads in {16, 32, 64}, L <= 1024.  bf16 at the model's (L, D) pairs runs on MFMA; every other call
+   (fp32, other L, unaligned pointers) takes a scalar kernel that holds one head's K and V in 8 L D bytes of LDS
+   (backward: 8 L (D + 1)) and is refused with MG_ERR_ARG above 65536 bytes. */
 int mg_attn_fwd(int dtype, const void* qkv, int B, int L, int C, int heads, void* out, float* lse, void* stream);
 
 /* Self-attention backward -> gqkv [B*L, 3C]. */

@@ -549,6 +549,10 @@ extern "C" int mg_layernorm_bwd(int dtype, int gy_dtype, const void* gy, int64_t
   return mg_check_launch("mg_layernorm_bwd");
 }
 
+// Dynamic LDS a kernel can be launched with unless hipFuncSetAttribute raises it; the scalar attention kernels keep
+// this default (the model needs at most 32 KiB, CLIP 25.6 KiB) and their launchers refuse larger shapes.
+static constexpr size_t kAttnScalarLds = 65536;
+
 int mg_attn_fwd_mfma(const void* qkv, int B, int L, int C, int heads, void* out, float* lse, hipStream_t st);
 int mg_attn_bwd_mfma(const void* qkv, const void* out, const void* gout, const float* lse, int B, int L, int C,
                      int heads, void* gqkv, hipStream_t st);
@@ -565,6 +569,8 @@ extern "C" int mg_attn_fwd(int dtype, const void* qkv, int B, int L, int C, int 
   }
   int thr = std::max(64, ((L + 63) / 64) * 64);
   size_t sm = 2 * (size_t)L * D * sizeof(float);
+  MG_REQUIRE(sm <= kAttnScalarLds, "the scalar kernel holds K and V of one head in LDS (8 L D bytes): over the 65536-byte "
+                                   "limit of dynamic LDS (fp32 or unaligned inputs: L D <= 8192)");
 #define L_(T, DD) hipLaunchKernelGGL((k_attn_fwd<T, DD>), dim3(B * heads), dim3(thr), sm, st, (const T*)qkv, L, C, heads, (T*)out, lse)
   if (dtype == MG_F32) {
     if (D == 16) L_(float, 16); else if (D == 32) L_(float, 32); else L_(float, 64);
@@ -587,6 +593,9 @@ extern "C" int mg_attn_bwd(int dtype, int gout_dtype, const void* qkv, const voi
   }
   int thr = std::max(64, ((L + 63) / 64) * 64);
   size_t sm = (2 * (size_t)L * D + 2 * (size_t)L) * sizeof(float);
+  MG_REQUIRE(sm <= kAttnScalarLds, "the scalar kernel holds two [L, D] operands, lse and delta of one head in LDS "
+                                   "(8 L (D + 1) bytes): over the 65536-byte limit of dynamic LDS (fp32, mixed gout "
+                                   "or unaligned inputs: L (D + 1) <= 8192)");
 #define L_(T, TG, DD) hipLaunchKernelGGL((k_attn_bwd<T, TG, DD>), dim3(B * heads), dim3(thr), sm, st, (const T*)qkv, \
                                          (const T*)out, (const TG*)gout, lse, L, C, heads, (T*)gqkv)
 #define LD_(T, TG) if (D == 16) L_(T, TG, 16); else if (D == 32) L_(T, TG, 32); else L_(T, TG, 64)

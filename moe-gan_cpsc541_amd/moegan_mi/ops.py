@@ -773,20 +773,29 @@ def modconv_bwd_data(gyt, w, k, B, H, W, Cin, x, s, gx, gs, accumulate=0, gxt_f3
 # ---------------------------------------------------------------------------
 # norm / attention
 # ---------------------------------------------------------------------------
+def _row_pitch(t, what):
+    """Row pitch (elements) of the token rows ``t`` [R, C]: its row stride, so a column slice of a wider buffer is
+    read at its own rows (shape[-1] when there is one row); the channels themselves must be contiguous."""
+    if t.shape[-1] > 1 and t.stride(-1) != 1:
+        raise L.MGError(f"layernorm: {what} needs contiguous channels (last-dimension stride {t.stride(-1)})")
+    return t.stride(0) if t.dim() == 2 and t.shape[0] > 1 else t.shape[-1]
+
+
 def layernorm_fwd(x, gamma, beta, eps=1e-5, act=0, out=None):
     R, C = x.shape[0], x.shape[-1]
-    out = torch.empty_like(x) if out is None else out
+    out = torch.empty_like(x, memory_format=torch.contiguous_format) if out is None else out
     mean = torch.empty(R, device=x.device, dtype=torch.float32)
     rstd = torch.empty(R, device=x.device, dtype=torch.float32)
-    call("mg_layernorm_fwd", dt(x), ptr(x), x.shape[-1], R, C, ptr(gamma), ptr(beta), eps, ptr(out), out.shape[-1],
-         ptr(mean), ptr(rstd), act, S())
+    call("mg_layernorm_fwd", dt(x), ptr(x), _row_pitch(x, "x"), R, C, ptr(gamma), ptr(beta), eps, ptr(out),
+         _row_pitch(out, "out"), ptr(mean), ptr(rstd), act, S())
     return out, mean, rstd
 
 
 def layernorm_bwd(gy, x, mean, rstd, gamma, gx, ggamma, gbeta, accumulate=0):
     R, C = x.shape[0], x.shape[-1]
-    call("mg_layernorm_bwd", dt(x), dt(gy), ptr(gy), gy.shape[-1], ptr(x), x.shape[-1], R, C, ptr(mean), ptr(rstd),
-         ptr(gamma), ptr(gx), gx.shape[-1] if gx is not None else 0, accumulate, ptr(ggamma), ptr(gbeta), S())
+    call("mg_layernorm_bwd", dt(x), dt(gy), ptr(gy), _row_pitch(gy, "gy"), ptr(x), _row_pitch(x, "x"), R, C,
+         ptr(mean), ptr(rstd), ptr(gamma), ptr(gx), _row_pitch(gx, "gx") if gx is not None else 0, accumulate,
+         ptr(ggamma), ptr(gbeta), S())
 
 
 def attn_fwd(qkv, B, L, C, heads=8):

@@ -25,6 +25,11 @@ assert_bf16 adds 2^-8 |ref|, one bf16 ulp for the final store; its reference is 
 bf16-rounded inputs the kernel reads.
 
 Both print the worst error / bound ratio of the check (pytest -s) and keep it in RATIOS per kernel name.
+
+LayerNorm and the self-attention core (mg_attn.hip, mg_attn_mfma.hip) come last in this file with bounds of their own
+(layernorm_*_bounds, attn_*_bounds: the rounding counts stand in their docstrings), checked through assert_bound.  Their
+backward references take the kernels' own inputs -- the saved mean / rstd, the forward's out and lse -- and restate the
+gradient as a function of those; the CPU file shows each to equal fp64 autograd when those inputs are exact.
 """
 import torch
 import torch.nn.functional as F
@@ -326,3 +331,209 @@ def adamw(p, g, m, v, lr, b1, b2, eps, wd, step, sumsq=None, max_norm=0.0):
     bc1, bc2 = 1.0 - b1 ** step, 1.0 - b2 ** step
     denom = v.sqrt() / bc2 ** 0.5 + eps
     return p - lr / bc1 * m / denom, m, v, coef
+
+
+# ---------------------------------------------------------------------------
+# LayerNorm (nn.LayerNorm over the last dim, :505-507; text_projection's LayerNorm + LeakyReLU, :684)
+# ---------------------------------------------------------------------------
+HW_ULP = 2 * U  # v_rsq_f32 / v_rcp_f32 / v_exp_f32 / v_log_f32: 1 ulp each is ASSUMED (the figure of AMD's ISA manuals
+#                 for the transcendental unit; no accuracy table for these instructions ships with the toolchain);
+#                 rsqrtf is also 1 ulp in the device-library table the module docstring cites
+
+
+def layernorm_fwd_ref(x, gamma, beta, eps, act=0, slope=0.2):
+    """y = (x - mean) rstd gamma + beta over the last dim, biased variance, rstd = (var + eps)^-1/2; act = 1 adds
+    LeakyReLU(slope).  Returns y, mean [R], rstd [R]."""
+    mean = x.mean(1)
+    xc = x - mean[:, None]
+    rstd = ((xc * xc).mean(1) + eps).rsqrt()
+    y = xc * rstd[:, None] * gamma + beta
+    return (F.leaky_relu(y, slope) if act else y), mean, rstd
+
+
+def ln_depth(C, vector):
+    """Additions a term of a C-term row sum passes through in the kernels: the vector kernels add 8 values per lane and
+    fold C / 8 lanes by xor-shuffles; the scalar ones add C / 64 per lane and fold the 64 lanes of a wave."""
+    return 8 + (C // 8).bit_length() - 1 if vector else C // 64 + 6
+
+
+def layernorm_fwd_bounds(x, gamma, beta, eps, act, depth, bf16_out):
+    """Bounds on |mean - ref|, |rstd - ref|, |y - ref| from fp64 quantities (x: what the kernel reads).
+    mean: every term passes ``depth`` additions and the division by C: (depth + 1) u sum|x| / C.
+    var:  sum (x - mean_k)^2 / C = var + (mean_k - mean)^2 exactly (the cross term vanishes), so the mean's error enters
+          squared; each square carries 3 roundings (the difference, twice, and the product), then depth + 1 as above;
+          one more rounding for + eps.
+    rstd: d rstd = -rstd / 2 d(var + eps) / (var + eps), plus rsqrtf's 1 ulp.
+    y:    gamma (rstd e_mean + |x - mean| e_rstd) + 3 u |(x - mean) rstd gamma| (difference, two products) + u |y| for
+          the addition of beta; LeakyReLU is 1-Lipschitz and adds one rounding; + 2^-8 |y| for a bf16 store."""
+    C = x.shape[1]
+    y, mean, rstd = layernorm_fwd_ref(x, gamma, beta, eps, 0)
+    xc = x - mean[:, None]
+    var = (xc * xc).mean(1)
+    e_mean = (depth + 1) * U * x.abs().sum(1) / C
+    e_var = (depth + 4) * U * (var + e_mean ** 2) + e_mean ** 2 + U * (var + eps)
+    e_rstd = rstd * (0.5 * e_var / (var + eps) + HW_ULP)
+    prod = (xc * rstd[:, None] * gamma).abs()
+    e_y = gamma.abs() * (rstd * e_mean + e_rstd * (1 + U))[:, None] + gamma.abs() * xc.abs() * e_rstd[:, None] \
+        + 3 * U * prod + U * y.abs()
+    if act:
+        e_y = e_y + U * y.abs()
+    ya = F.leaky_relu(y, 0.2).abs() if act else y.abs()
+    b_y = e_y * (1 + 2.0 ** -8) + 2 * U * ya + TINY + (2.0 ** -8 * ya if bf16_out else 0.0)
+    return e_mean + U * mean.abs() + TINY, e_rstd + U * rstd, b_y
+
+
+def layernorm_bwd_ref(gy, x, mean, rstd, gamma):
+    """With xh = (x - mean) rstd and gh = gy gamma: gx = rstd (gh - mean_c gh - xh mean_c(gh xh)),
+    ggamma = sum_r gy xh, gbeta = sum_r gy.  mean and rstd are inputs (what the forward saved)."""
+    xh = (x - mean[:, None]) * rstd[:, None]
+    gh = gy * gamma
+    s1 = gh.mean(1, keepdim=True)
+    s2 = (gh * xh).mean(1, keepdim=True)
+    return rstd[:, None] * (gh - s1 - xh * s2), (gy * xh).sum(0), gy.sum(0)
+
+
+def layernorm_bwd_bounds(gy, x, mean, rstd, gamma, depth, n_col, base=None, pre=None, bf16_out=False):
+    """Bounds on gx, ggamma, gbeta.  xh carries 2 roundings, gh 1; s1 = sum gh / C: (depth + 2) u sum|gh| / C;
+    s2 = sum gh xh / C: 4 roundings per product, (depth + 5) u sum|gh xh| / C.  gx: each of gh, s1, xh s2 passes at most
+    5 further roundings (xh twice, the product, two subtractions, the product with rstd) on top of e_s1 and |xh| e_s2;
+    + u |gx + base| when accumulating.  ggamma / gbeta: ``n_col`` additions per term (counted by the caller from the
+    launch) + 3 roundings per product + 1 for the sum onto ``pre``, n u sum_r|term|."""
+    C = x.shape[1]
+    gx, gg, gb = layernorm_bwd_ref(gy, x, mean, rstd, gamma)
+    xh = (x - mean[:, None]) * rstd[:, None]
+    gh = gy * gamma
+    s1 = gh.mean(1, keepdim=True)
+    s2 = (gh * xh).mean(1, keepdim=True)
+    e_s1 = (depth + 2) * U * gh.abs().sum(1, keepdim=True) / C
+    e_s2 = (depth + 5) * U * (gh * xh).abs().sum(1, keepdim=True) / C
+    T = gh.abs() + s1.abs() + (xh * s2).abs()
+    e_gx = rstd[:, None] * (5 * U * T + e_s1 + xh.abs() * e_s2)
+    ref = gx if base is None else gx + base
+    b_gx = e_gx * (1 + 2.0 ** -8) + 2 * U * ref.abs() + TINY + (2.0 ** -8 * ref.abs() if bf16_out else 0.0)
+    pg, pb = (0.0, 0.0) if pre is None else (abs(pre[0]), abs(pre[1]))
+    b_gg = (n_col + 4) * U * ((gy * xh).abs().sum(0) + pg) + TINY
+    b_gb = (n_col + 1) * U * (gy.abs().sum(0) + pb) + TINY
+    return b_gx, b_gg, b_gb
+
+
+# ---------------------------------------------------------------------------
+# self-attention core of nn.MultiheadAttention (:513, :546) on packed qkv [B L, 3 C] (q | k | v, head h at h D)
+# ---------------------------------------------------------------------------
+def _heads(t, B, L, heads):
+    """[B L, heads D] -> [B, heads, L, D]."""
+    return t.view(B, L, heads, -1).permute(0, 2, 1, 3)
+
+
+def _rows(t, B, L):
+    """[B, heads, L, D] -> [B L, heads D]."""
+    return t.permute(0, 2, 1, 3).reshape(B * L, -1)
+
+
+def attn_fwd_ref(qkv, B, L, C, heads):
+    """out = softmax(q k^T / sqrt(D)) v per (image, head).  Returns out [B L, C], lse [B, heads, L] and the
+    probabilities P [B, heads, L, L]."""
+    D = C // heads
+    q, k, v = (_heads(qkv[:, i * C:(i + 1) * C], B, L, heads) for i in range(3))
+    s = q @ k.transpose(-1, -2) / D ** 0.5
+    lse = torch.logsumexp(s, -1)
+    P = (s - lse[..., None]).exp()
+    return _rows(P @ v, B, L), lse, P
+
+
+def attn_bwd_ref(qkv, out, lse, gout, B, L, C, heads):
+    """The backward as a function of its four inputs (out and lse as handed to the kernel, not recomputed):
+    P = exp(s - lse), delta_i = sum_c out_ic g_ic, dS = P (g v^T - delta), dQ = scale dS K, dK = scale dS^T Q,
+    dV = P^T g.  Returns gqkv [B L, 3 C]."""
+    D = C // heads
+    scale = D ** -0.5
+    q, k, v = (_heads(qkv[:, i * C:(i + 1) * C], B, L, heads) for i in range(3))
+    o, g = _heads(out, B, L, heads), _heads(gout, B, L, heads)
+    P = (q @ k.transpose(-1, -2) * scale - lse[..., None]).exp()
+    delta = (o * g).sum(-1, keepdim=True)
+    dS = P * (g @ v.transpose(-1, -2) - delta)
+    return torch.cat([_rows(scale * dS @ k, B, L), _rows(scale * dS.transpose(-1, -2) @ q, B, L),
+                      _rows(P.transpose(-1, -2) @ g, B, L)], 1)
+
+
+def _attn_eps(q, k, s, lse, scale, mfma):
+    """Per query row [B, heads, L, 1]: eps_s, the error of a scaled score, and eps_p, the relative error of a
+    recomputed probability exp(s - M) (M: the row's max or lse).
+    eps_s = n_D u scale max_j sum_d |q_d k_d|: bf16 products are exact in fp32, so the MFMA's D-term accumulation is
+    n_D = D roundings; the scalar kernels round q scale and every product as well, n_D = D + 2.
+    eps_p = eps_s + 6 u Smax + 1 ulp, Smax = max(max_j |s_ij|, |lse_i|): the exponent's argument is fma(s, k2, -M k2) in
+    log2 units (scalar: (s - M) log2 e) -- one rounding each for k2 = scale log2 e, the constant, M k2 and the fma (or
+    the subtraction and the product), each at most u Smax or u |s - M| <= 2 u Smax, and rsqrtf(D)'s 1 ulp on scale (2 u
+    |s|); then v_exp_f32's own 1 ulp (ASSUMED, see HW_ULP).  The score's own error enters once: the row maximum's is
+    common to the row and cancels between numerator and denominator (and between m and log l in lse)."""
+    D = q.shape[-1]
+    n_D = D if mfma else D + 2
+    eps_s = n_D * U * scale * (q.abs() @ k.abs().transpose(-1, -2)).amax(-1, keepdim=True)
+    smax = torch.maximum(s.abs().amax(-1, keepdim=True), lse.abs()[..., None])
+    return eps_s, eps_s + 6 * U * smax + HW_ULP
+
+
+def attn_fwd_bounds(qkv, B, L, C, heads, mfma, bf16_out):
+    """Bounds on |out - ref| [B L, C] and |lse - ref| [B, heads, L] (see _attn_eps for eps_p), A = sum_j P_ij |v_jc|:
+      out: (eps_p + bf + n_acc u) A + (eps_p + n_l u + 3 u) |out| + store
+           numerator: every p_ij off by eps_p, rounded to bf16 for the MFMA (bf = 2^-8; 0 for the scalar kernel), n_acc
+           accumulation roundings; denominator l: eps_p and n_l additions; 1 / l (v_rcp_f32, 1 ulp ASSUMED) and the
+           product: 3 u.  MFMA: n_acc = L (fp32 accumulate over the keys, any order), n_l = L / 4 + 2 (a lane adds its
+           L / 4 probabilities, two shuffles).  Scalar (online softmax, serial over the keys): each of the L steps
+           rounds the rescale and the addition and may rescale by a corr = exp(m - m') that is off by 1 ulp + argument
+           roundings (those, summed over a row, telescope to <= 2 u Smax, inside eps_p's 6 u Smax): n_acc = n_l = 5 L.
+      lse: eps_p + n_l u (relative error of l = absolute error of log l) + 4 u Smax (m scale, and the M of _attn_eps
+           against it) + logf = v_log_f32 ln 2: (1 ulp ASSUMED + 2 u) |log l| + 2 u absolute + u |lse| for the sum."""
+    D = C // heads
+    scale = D ** -0.5
+    out, lse, P = attn_fwd_ref(qkv, B, L, C, heads)
+    q, k, v = (_heads(qkv[:, i * C:(i + 1) * C], B, L, heads) for i in range(3))
+    s = q @ k.transpose(-1, -2) * scale
+    eps_s, eps_p = _attn_eps(q, k, s, lse, scale, mfma)
+    n_acc, n_l = (L, L // 4 + 2) if mfma else (5 * L, 5 * L)
+    A = P @ v.abs()
+    o = _heads(out, B, L, heads).abs()
+    b_out = (eps_p + (2.0 ** -8 if mfma else 0.0) + n_acc * U) * A + (eps_p + (n_l + 3) * U) * o
+    b_out = _rows(b_out, B, L) * (1 + 2.0 ** -8) + 2 * U * out.abs() + TINY
+    if bf16_out:
+        b_out = b_out + 2.0 ** -8 * out.abs()
+    smax = torch.maximum(s.abs().amax(-1), lse.abs())
+    logl = lse - s.amax(-1)
+    b_lse = eps_p[..., 0] + n_l * U + 4 * U * smax + 4 * U * logl.abs() + 2 * U + 2 * U * lse.abs() + TINY
+    return b_out, b_lse
+
+
+def attn_bwd_bounds(qkv, out, lse, gout, B, L, C, heads, mfma, bf16_out):
+    """Bound on |gqkv - attn_bwd_ref| [B L, 3 C].  Per element of dS = P (dP - delta):
+      e_ij = P_ij E_i + (eps_p + 2 u) P_ij (|dP_ij| + |delta_i|) + n_D u P_ij sum_c |g_ic| |v_jc| + bf |dS_ij|
+    E_i = (D + 1) u sum_c |out_ic g_ic| (delta's D-term fp32 sum), eps_p from _attn_eps with M = lse, 2 u for the
+    subtraction and the product, n_D as in _attn_eps for dP, bf = 2^-8 where dS and P become bf16 MFMA operands.
+      dQ: scale sum_j e_ij |k_jc| + L u scale sum_j |dS_ij| |k_jc| (accumulation over the keys) + 3 u |dQ| (scale: a
+          product and rsqrtf's ulp);  dK alike over i with |q|;
+      dV: sum_i (bf + eps_p) P_ij |g_ic| + L u sum_i P_ij |g_ic|;  each + 2^-8 |ref| for a bf16 store."""
+    D = C // heads
+    scale = D ** -0.5
+    ref = attn_bwd_ref(qkv, out, lse, gout, B, L, C, heads)
+    q, k, v = (_heads(qkv[:, i * C:(i + 1) * C], B, L, heads) for i in range(3))
+    o, g = _heads(out, B, L, heads), _heads(gout, B, L, heads)
+    s = q @ k.transpose(-1, -2) * scale
+    P = (s - lse[..., None]).exp()
+    _, eps_p = _attn_eps(q, k, s, lse, scale, mfma)
+    n_D = D if mfma else D + 2
+    bf = 2.0 ** -8 if mfma else 0.0
+    delta = (o * g).sum(-1, keepdim=True)
+    dP = g @ v.transpose(-1, -2)
+    dS = P * (dP - delta)
+    E = (D + 1) * U * (o * g).abs().sum(-1, keepdim=True)
+    e = P * E + (eps_p + 2 * U) * P * (dP.abs() + delta.abs()) + n_D * U * P * (g.abs() @ v.abs().transpose(-1, -2)) \
+        + bf * dS.abs()
+    b_q = scale * (e @ k.abs()) + L * U * scale * (dS.abs() @ k.abs())
+    b_k = scale * (e.transpose(-1, -2) @ q.abs()) + L * U * scale * (dS.abs().transpose(-1, -2) @ q.abs())
+    b_v = ((bf + eps_p + L * U) * P).transpose(-1, -2) @ g.abs()
+    b = torch.cat([_rows(b_q, B, L), _rows(b_k, B, L), _rows(b_v, B, L)], 1)
+    return ref, b * (1 + 2.0 ** -8) + 3 * U * ref.abs() + TINY + (2.0 ** -8 * ref.abs() if bf16_out else 0.0)
+
+
+def assert_bound(out, ref, bound, name="?"):
+    """|out - ref| <= bound elementwise, with the ratio printed and recorded like assert_fp32's."""
+    return _check(name, out, ref, bound)

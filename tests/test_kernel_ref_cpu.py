@@ -205,3 +205,51 @@ def test_head_and_text_branch_match_autograd():
     g_tpre, dW2t, _ = R.d_text_bwd(gl.sum(1), t.detach(), w2sum)
     _close(g_tpre, tpre.grad, "g_tpre")
     _close(dW2t, W.grad[0, Cf:].reshape(Ct, 16), "dW2 text rows")
+
+
+@pytest.mark.parametrize("R_,C,act", [(1, 128, 0), (5, 256, 1), (3, 768, 0)])
+def test_layernorm_references_match_torch(R_, C, act):
+    g = torch.Generator().manual_seed(R_ + C)
+    x = (_rand(g, R_, C) * 2 + 0.5).requires_grad_()
+    gamma = (torch.rand(C, generator=g, dtype=D) + 0.5).requires_grad_()
+    beta = _rand(g, C).requires_grad_()
+    eps = 1e-3
+    y = F.layer_norm(x, (C,), gamma, beta, eps)
+    want = F.leaky_relu(y, 0.2) if act else y
+    got, mean, rstd = R.layernorm_fwd_ref(x.detach(), gamma.detach(), beta.detach(), eps, act, 0.2)
+    _close(got, want.detach(), "y")
+    _close(mean, x.detach().mean(1), "mean")
+    _close(rstd, (x.detach().var(1, unbiased=False) + eps).rsqrt(), "rstd")
+    gy = _rand(g, R_, C)
+    (y * gy).sum().backward()  # the backward kernel differentiates the plain LayerNorm (act = 0)
+    gx, gg, gb = R.layernorm_bwd_ref(gy, x.detach(), mean, rstd, gamma.detach())
+    _close(gx, x.grad, "gx")
+    _close(gg, gamma.grad, "ggamma")
+    _close(gb, beta.grad, "gbeta")
+
+
+def test_layernorm_reference_constant_row_and_eps():
+    x = torch.full((2, 128), 3.25, dtype=D)
+    one = torch.ones(128, dtype=D)
+    y, mean, rstd = R.layernorm_fwd_ref(x, one, 0 * one, 0.25)
+    assert torch.equal(mean, torch.full((2,), 3.25, dtype=D)) and torch.equal(rstd, torch.full((2,), 2.0, dtype=D))
+    assert torch.equal(y, torch.zeros_like(y))
+
+
+@pytest.mark.parametrize("B,L,heads,Dh", [(1, 1, 1, 16), (2, 5, 3, 16), (3, 17, 2, 32)])
+def test_attention_references_match_autograd(B, L, heads, Dh):
+    """attn_fwd_ref against F.scaled_dot_product-style softmax attention, and attn_bwd_ref -- a function of qkv, out,
+    lse, gout -- fed the exact out and lse, against fp64 autograd: restated on exact inputs it is the gradient."""
+    g = torch.Generator().manual_seed(B * 10 + L)
+    C = heads * Dh
+    qkv = (_rand(g, B * L, 3 * C) * 1.5).requires_grad_()
+    x = qkv.view(B, L, 3, heads, Dh).permute(2, 0, 3, 1, 4)
+    s = x[0] @ x[1].transpose(-1, -2) / Dh ** 0.5
+    o = (torch.softmax(s, -1) @ x[2]).permute(0, 2, 1, 3).reshape(B * L, C)
+    gout = _rand(g, B * L, C)
+    (o * gout).sum().backward()
+    out, lse, P = R.attn_fwd_ref(qkv.detach(), B, L, C, heads)
+    _close(out, o.detach(), "out")
+    _close(lse, torch.logsumexp(s.detach(), -1), "lse")
+    _close(P, torch.softmax(s.detach(), -1), "P")
+    _close(R.attn_bwd_ref(qkv.detach(), out, lse, gout, B, L, C, heads), qkv.grad, "gqkv")
