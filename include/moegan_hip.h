@@ -398,6 +398,35 @@ int mg_modconv_bwd_in(int gxt_dtype, const void* gxt, int64_t ld_gxt, int dtype,
    Cin % 8, Cout below one K step (3x3), a bf16 gx from fp32 operands, unaligned s / x / gx. */
 int mg_modconv_dgrad_fusable(int dtype, int gx_dtype, int k, int B, int H, int W, int Cout, int Cin, const float* s, int64_t ld_s, const void* x, int64_t ld_x, const void* gx, int64_t ld_gx);
 
+/* Weight gradients that also leave the layer's bias gradient: the same calls as mg_conv2d_wgrad,
+   mg_gemm_grouped_wgrad, mg_d0_wgrad and mg_gemm's weight-gradient form (same arguments, same weight-gradient
+   results), plus
+     bias_out[o] += sum over pixels of gy[p, o]                      (conv, d0: o < Cout / 128)
+     bias_out[m] += sum over k of A[k, m]                             (mg_gemm_wgrad_bias)
+     bias_out[g * M + m] += sum over the rows r of group g of A[r, m] (grouped; an empty group's row is not touched)
+   taken in fp32 from the operand fragments of the weight gradient's own K loop (one more MFMA against a fragment of
+   ones; fp32 atomics per block), so no separate column sum reads the output gradient again.  bias_out is accumulated
+   into, like the weight gradient.  The *_fusable predicates are the library's own answer whether a call is covered
+   (1) or the caller runs the plain entry and mg_colsum / mg_grouped_colsum (0); a call they refuse is an argument
+   error.  Not covered: deterministic mode, tuning slot 30 = 1, operands other than bf16, modulated inputs
+   (in_scale), 1x1 / stride-1 convs (the long-reduction kernel), the direct 32-channel 3x3 weight gradient, forced
+   256-wide tiles, a loader transform on A (a_idx / a_rowscale / a_gelu; b_idx / b_gelu on B are fine). */
+int mg_conv2d_wgrad_bias_fusable(int dtype, int H, int W, int Cin, const float* in_scale, int Cout, int KH, int KW, int stride, int pad);
+int mg_conv2d_wgrad_bias(int dtype, const void* gy, int64_t ldg, const void* x, int B, int H, int W, int Cin,
+                         const float* in_scale, int Cout, int KH, int KW, int stride, int pad, float* gw, int splits,
+                         float* bias_out, void* stream);
+int mg_gemm_grouped_wgrad_bias_fusable(int dtype, const mg_epilogue* ep);
+int mg_gemm_grouped_wgrad_bias(int dtype, int M, int N, int ngroups, const int32_t* row_off, int total_rows,
+                               const void* A, int64_t lda, const void* B, int64_t ldb, const int32_t* b_idx,
+                               int b_idx_div, int b_gelu, float* C, int splits, const mg_epilogue* ep,
+                               float* bias_out, void* stream);
+int mg_gemm_wgrad_bias_fusable(int dtype);
+/* mg_gemm(MG_BF16, M, N, K, A, lda, 0, B, ldb, 0, C, ldc, MG_F32, {alpha, atomic = 1}, splits) + bias_out */
+int mg_gemm_wgrad_bias(int dtype, int M, int N, int K, const void* A, int64_t lda, const void* B, int64_t ldb,
+                       float* C, int64_t ldc, float alpha, int splits, float* bias_out, void* stream);
+int mg_d0_wgrad_bias_fusable(void);
+int mg_d0_wgrad_bias(int in_dtype, const void* x, int64_t sb, int64_t sh, int64_t sw, int64_t sc, int B, int H, int W, const void* g, float* dw, float* bias_out, void* stream);
+
 /* Generator KL total and per-router gradient coefficients (total clamped at 50, t2i_moe_gan.py:1369-1370). */
 int mg_kl_coefs(const float* kl2, int R, float eff_w, float* coef, float* total, void* stream);
 

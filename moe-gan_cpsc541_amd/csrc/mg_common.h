@@ -171,7 +171,8 @@ enum { MG_TUNE_WGRAD_TILE = 0, MG_TUNE_GWGRAD_TILE = 1, MG_TUNE_CONV_TILE = 2, M
        MG_TUNE_WIDE_BLOCKS = 27,     // mg_wgrad_wide.hip grid target (blocks): 0 automatic (256)
        MG_TUNE_WGRAD_SLAB_BLOCKS = 28,  // conv weight-gradient slab split target (blocks): 0 automatic (1024)
        MG_TUNE_MODGRAD_UNFUSED = 29,  // 1: the modulated conv's gx / gs as mg_modconv_bwd_in after the data-gradient GEMM, never in its epilogue (A/B)
-       MG_TUNE_COUNT = 30 };
+       MG_TUNE_WGRAD_BIAS_UNFUSED = 30,  // 1: bias gradients by the separate column sums, never from the weight-gradient kernels' K loop (A/B)
+       MG_TUNE_COUNT = 31 };
 extern std::atomic<int> g_mg_tune[MG_TUNE_COUNT];
 // Deterministic mode (mg_set_tuning(MG_TUNE_DETERMINISTIC, 1)): every reduction that crosses workgroups runs in
 // a fixed order -- per-block partial rows in the stream's workspace folded by one pass, or one writer per
@@ -262,4 +263,4 @@ int mg_modgrad_conv(int dtype, const void* x, int B, int H, int W, int Cin, cons
 
 // mg_wgrad_wide.hip: wide split-K weight gradients (bf16 [K][M] x [K][N] -> fp32 C +=), true when handled
 bool mg_wgrad_wide(int M, int N, int K, const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t ldc,
-                   float alpha, hipStream_t st);
+                   float alpha, hipStream_t st, float* bias_out = nullptr);

@@ -334,10 +334,14 @@ __global__ __launch_bounds__(D0_T) void k_d0_fwd(const TI* __restrict__ x, int64
 constexpr int G_LD = 160;  // MC image pitches (bf16): odd multiples of 16 dwords
 constexpr int X_LD = 96;
 
-template <typename TI, int NRO>
-__global__ __launch_bounds__(D0_T) void k_d0_wgrad(const TI* __restrict__ x, int64_t sb, int64_t sh, int64_t sw,
-                                                   int64_t sc, int H, int P, const bf16_t* __restrict__ g,
-                                                   float* __restrict__ part) {
+// BG: also the bias gradient bias_out[o] += sum over pixels of g[:, o].  The fourth B fragment (k = 48..63) is padding
+// that the plain kernel multiplies and drops; BG feeds bf16 ones there instead of reading it, so acc[mf][3] holds the
+// row sums of the gradient fragments (every column the same); column 0's lanes store them as 128 more columns of the
+// block's partial row, and the fixed-order fold of the partials delivers them (k_fold_cols_split).  (As one fp32 atomic
+// per channel and block the 512 blocks queued on the same 128 addresses: 21 -> 67 us at B = 256.)
+template <typename TI, int NRO, bool BG>
+MG_DEV void d0_wgrad_body(const TI* __restrict__ x, int64_t sb, int64_t sh, int64_t sw, int64_t sc, int H, int P,
+                          const bf16_t* __restrict__ g, float* __restrict__ part) {
   using RW = Rows<NRO>;
   __shared__ bf16_t Gs[D0_BM * G_LD];
   __shared__ bf16_t Xp[D0_BM * X_LD];
@@ -386,7 +390,8 @@ __global__ __launch_bounds__(D0_T) void k_d0_wgrad(const TI* __restrict__ x, int
 #pragma unroll
       for (int mf = 0; mf < 2; ++mf) a[mf] = mc_frag(Gs, G_LD, 32 * ks, 32 * w + 16 * mf, lane);
 #pragma unroll
-      for (int nf = 0; nf < 4; ++nf) b[nf] = mc_frag(Xp, X_LD, 32 * ks, 16 * nf, lane);
+      for (int nf = 0; nf < (BG ? 3 : 4); ++nf) b[nf] = mc_frag(Xp, X_LD, 32 * ks, 16 * nf, lane);
+      if constexpr (BG) b[3] = __builtin_bit_cast(bf16x8_t, u16x8_t(0x3F80));  // bf16 1.0 in every k slot
 #pragma unroll
       for (int mf = 0; mf < 2; ++mf)
 #pragma unroll
@@ -395,7 +400,7 @@ __global__ __launch_bounds__(D0_T) void k_d0_wgrad(const TI* __restrict__ x, int
     }
   }
   // this block's partial: acc[mf][nf][j] = dW[o = 32w + 16mf + 4(lane>>4) + j][k = 16nf + (lane&15)], k < 48
-  float* pb = part + (int64_t)blockIdx.x * (128 * 48);
+  float* pb = part + (int64_t)blockIdx.x * (128 * 48 + (BG ? 128 : 0));
 #pragma unroll
   for (int mf = 0; mf < 2; ++mf)
 #pragma unroll
@@ -405,6 +410,27 @@ __global__ __launch_bounds__(D0_T) void k_d0_wgrad(const TI* __restrict__ x, int
         const int o = 32 * w + 16 * mf + 4 * (lane >> 4) + j, k = 16 * nf + (lane & 15);
         pb[o * 48 + k] = acc[mf][nf][j];
       }
+  if constexpr (BG) {
+    if ((lane & 15) == 0) {
+#pragma unroll
+      for (int mf = 0; mf < 2; ++mf)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) pb[128 * 48 + 32 * w + 16 * mf + 4 * (lane >> 4) + j] = acc[mf][3][j];
+    }
+  }
+}
+
+template <typename TI, int NRO>
+__global__ __launch_bounds__(D0_T) void k_d0_wgrad(const TI* __restrict__ x, int64_t sb, int64_t sh, int64_t sw,
+                                                   int64_t sc, int H, int P, const bf16_t* __restrict__ g,
+                                                   float* __restrict__ part) {
+  d0_wgrad_body<TI, NRO, false>(x, sb, sh, sw, sc, H, P, g, part);
+}
+template <typename TI, int NRO>
+__global__ __launch_bounds__(D0_T) void k_d0_wgrad_bias(const TI* __restrict__ x, int64_t sb, int64_t sh, int64_t sw,
+                                                        int64_t sc, int H, int P, const bf16_t* __restrict__ g,
+                                                        float* __restrict__ part) {
+  d0_wgrad_body<TI, NRO, true>(x, sb, sh, sw, sc, H, P, g, part);
 }
 
 // first level of the partial fold: tmp[y][i] = sum of rows y*rpg .. (y+1)*rpg - 1 of part (fixed order)
@@ -425,6 +451,27 @@ __global__ __launch_bounds__(256) void k_fold_cols(const float* __restrict__ par
   for (; r < r1; ++r) s += part[(int64_t)r * ncols + i];
   if (accumulate) tmp[(int64_t)y * ncols + i] += s;
   else tmp[(int64_t)y * ncols + i] = s;
+}
+
+// last level of the fold for partial rows of nsplit + nb columns: the first nsplit go to out_a, the rest to out_b
+// (k_fold_cols' order, accumulating)
+__global__ __launch_bounds__(256) void k_fold_cols_split(const float* __restrict__ part, int nrows, int ncols,
+                                                         int nsplit, float* __restrict__ out_a,
+                                                         float* __restrict__ out_b) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= ncols) return;
+  float s = 0.f;
+  int r = 0;
+  for (; r + 8 <= nrows; r += 8) {
+    float v[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) v[q] = part[(int64_t)(r + q) * ncols + i];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) s += v[q];
+  }
+  for (; r < nrows; ++r) s += part[(int64_t)r * ncols + i];
+  if (i < nsplit) out_a[i] += s;
+  else out_b[i - nsplit] += s;
 }
 
 // image gradient: one block per (image, band of RI input rows)
@@ -593,8 +640,34 @@ extern "C" int mg_d0_fwd(int in_dtype, const void* x, int64_t sb, int64_t sh, in
   return mg_check_launch("mg_d0_fwd");
 }
 
+namespace {
+int d0_wgrad_impl(int in_dtype, const void* x, int64_t sb, int64_t sh, int64_t sw, int64_t sc, int B, int H, int W,
+                  const void* g, float* dw, float* bias_out, void* stream);
+}  // namespace
+
 extern "C" int mg_d0_wgrad(int in_dtype, const void* x, int64_t sb, int64_t sh, int64_t sw, int64_t sc, int B, int H,
                            int W, const void* g, float* dw, void* stream) {
+  return d0_wgrad_impl(in_dtype, x, sb, sh, sw, sc, B, H, W, g, dw, nullptr, stream);
+}
+
+// the bias sum rides in mg_d0_wgrad's K loop (k_d0_wgrad_bias) unless the library runs deterministic (one rule for
+// every *_wgrad_bias entry point, though this one's fold has a fixed order) or tuning slot MG_TUNE_WGRAD_BIAS_UNFUSED
+// is set
+extern "C" int mg_d0_wgrad_bias_fusable(void) {
+  return (mg_det() || g_mg_tune[MG_TUNE_WGRAD_BIAS_UNFUSED] != 0) ? 0 : 1;
+}
+
+extern "C" int mg_d0_wgrad_bias(int in_dtype, const void* x, int64_t sb, int64_t sh, int64_t sw, int64_t sc, int B,
+                                int H, int W, const void* g, float* dw, float* bias_out, void* stream) {
+  MG_REQUIRE(bias_out, "bias_out must be set");
+  MG_REQUIRE(mg_d0_wgrad_bias_fusable(),
+             "not covered (deterministic mode / MG_TUNE_WGRAD_BIAS_UNFUSED): run mg_d0_wgrad and mg_colsum");
+  return d0_wgrad_impl(in_dtype, x, sb, sh, sw, sc, B, H, W, g, dw, bias_out, stream);
+}
+
+namespace {
+int d0_wgrad_impl(int in_dtype, const void* x, int64_t sb, int64_t sh, int64_t sw, int64_t sc, int B, int H, int W,
+                  const void* g, float* dw, float* bias_out, void* stream) {
   MG_REQUIRE(B > 0, "B > 0");
   if (int rc = d0_layout(in_dtype, x, sb, sh, sw, sc, H, W)) return rc;
   MG_REQUIRE(mg_al16(g), "16-byte aligned gradient");
@@ -604,11 +677,16 @@ extern "C" int mg_d0_wgrad(int in_dtype, const void* x, int64_t sb, int64_t sh, 
   const int ntiles = cdiv(P, D0_BM);
   // two blocks per CU (73 KB of LDS each), ~4 tiles per block at B=256 64x64 (2048 tiles)
   const int grid = std::min(ntiles, 512);
-  const int ncols = 128 * 48, groups = std::min(grid, 32), rpg = cdiv(grid, groups);
+  // (with the bias gradient: 128 more columns per partial row)
+  const int ncols = 128 * 48 + (bias_out ? 128 : 0), groups = std::min(grid, 32), rpg = cdiv(grid, groups);
   float* part = reinterpret_cast<float*>(mg_workspace((size_t)(grid + groups) * ncols * sizeof(float), st));
   if (!part) return MG_ERR_ARG;
   float* tmp = part + (size_t)grid * ncols;
-#define L_(TI, NRO) hipLaunchKernelGGL((k_d0_wgrad<TI, NRO>), dim3(grid), dim3(D0_T), 0, st, (const TI*)x, sb, sh, sw, sc, H, (int)P, (const bf16_t*)g, part)
+#define L_(TI, NRO)                                                                                                 \
+  do {                                                                                                              \
+    if (bias_out) hipLaunchKernelGGL((k_d0_wgrad_bias<TI, NRO>), dim3(grid), dim3(D0_T), 0, st, (const TI*)x, sb, sh, sw, sc, H, (int)P, (const bf16_t*)g, part); \
+    else hipLaunchKernelGGL((k_d0_wgrad<TI, NRO>), dim3(grid), dim3(D0_T), 0, st, (const TI*)x, sb, sh, sw, sc, H, (int)P, (const bf16_t*)g, part); \
+  } while (0)
 #define F32_(NRO) L_(float, NRO)
 #define BF_(NRO) L_(bf16_t, NRO)
   if (in_dtype == MG_F32) { D0_NRO_SWITCH(W / 2, F32_) } else { D0_NRO_SWITCH(W / 2, BF_) }
@@ -617,9 +695,13 @@ extern "C" int mg_d0_wgrad(int in_dtype, const void* x, int64_t sb, int64_t sh, 
 #undef L_
   // fixed-order fold of the block partials: groups of rpg rows, then the groups
   hipLaunchKernelGGL(k_fold_cols, dim3(cdiv(ncols, 256), groups), dim3(256), 0, st, part, grid, ncols, rpg, tmp, 0);
-  hipLaunchKernelGGL(k_fold_cols, dim3(cdiv(ncols, 256), 1), dim3(256), 0, st, tmp, groups, ncols, groups, dw, 1);
+  if (bias_out)
+    hipLaunchKernelGGL(k_fold_cols_split, dim3(cdiv(ncols, 256)), dim3(256), 0, st, tmp, groups, ncols, 128 * 48, dw, bias_out);
+  else
+    hipLaunchKernelGGL(k_fold_cols, dim3(cdiv(ncols, 256), 1), dim3(256), 0, st, tmp, groups, ncols, groups, dw, 1);
   return mg_check_launch("mg_d0_wgrad");
 }
+}  // namespace
 
 extern "C" int mg_d0_dgrad(const void* g, int B, int OH, int OW, const void* w0p, int out_dtype, void* out,
                            int64_t ldo, void* stream) {

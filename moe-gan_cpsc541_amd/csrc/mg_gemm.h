@@ -761,6 +761,22 @@ struct EpiModGrad : Epi<TO> {
 template <class EP, class = void> struct has_colsum : std::false_type {};
 template <class EP> struct has_colsum<EP, std::void_t<decltype(EP::kColSum)>> : std::integral_constant<bool, EP::kColSum> {};
 
+// Weight gradient (C = A^T B over pixels / tokens, both operands MC) that also leaves the layer's bias gradient
+// bias_out[m] += sum_k A[k][m]: the product of the A fragments the K loop already holds with a B fragment of ones,
+// one more MFMA per A fragment in the waves that own column tile 0 (gemm_tile, kBiasGrad), so the separate column
+// sum's pass over the output gradient goes.  1.0 * a is exact and the sum is fp32, like the column-sum kernels'.
+// One fp32 atomic per row leaves each (row tile, K split); grouped-K launches add into row g of bias_out
+// (gstride_bo = M).  An epilogue type of its own for EpiQuickGeluGrad's reason: the plain kernels keep their
+// registers.  bf16 operands only (mg_*_wgrad_bias_fusable, mg_gemm.hip, admit the calls).
+template <typename TO>
+struct EpiBiasGrad : Epi<TO> {
+  static constexpr bool kBiasGrad = true;
+  float* bias_out; int64_t gstride_bo;
+  MG_DEV void bias_add(int m, float v) const { atomicAdd(bias_out + (int64_t)this->g * gstride_bo + m, v); }
+};
+template <class EP, class = void> struct has_biasgrad : std::false_type {};
+template <class EP> struct has_biasgrad<EP, std::void_t<decltype(EP::kBiasGrad)>> : std::integral_constant<bool, EP::kBiasGrad> {};
+
 // grouping descriptor (device tables)
 struct Grouping {
   int mode;              // 0 none, 1 grouped-M (rows), 2 grouped-K (reduction rows)
@@ -1171,6 +1187,23 @@ MG_DEV void gemm_tile(const AL& A, const BL& B, const EP& ep, int m0, int n0, in
     for (int j = 0; j < FN; ++j) acc[i][j] = f32x4_t{0.f, 0.f, 0.f, 0.f};
 
   const int fr = lane & 15, fq = lane >> 4;
+  // kBiasGrad epilogues (EpiBiasGrad): row sums of the A^T fragments against a B fragment of ones in the waves of
+  // column tile 0, of zeros in every other wave -- the MFMA is issued by all of them, so the K step stays one basic
+  // block (as a wave-uniform branch round the MFMAs it cost the 128^2 tiles 40 VGPRs and 44 AGPRs, one block per CU
+  // instead of two, and the discriminator's 4x4 weight gradient went from 93 to 166 us); the waves of a block meet at
+  // a barrier every K step anyway, so the step takes what its slowest wave takes either way
+  constexpr bool BG = has_biasgrad<EP>::value;
+  static_assert(!BG || (!A_KC && !B_KC && !X3 && sizeof(T) == 2), "bias gradient: bf16 weight-gradient tiles only");
+  f32x4_t bacc[BG ? FM : 1];
+  const bool bias_wave = BG && n0 == 0 && wn == 0;
+  // bf16 1.0 (bias waves) or 0 in every k slot
+  const bf16x8_t bias_b = __builtin_bit_cast(bf16x8_t, u16x8_t(bias_wave ? 0x3F80 : 0));
+  if constexpr (BG) {
+#pragma unroll
+    for (int i = 0; i < FM; ++i) bacc[i] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  }
+  (void)bacc;
+  (void)bias_b;
   // one K step of MFMAs from the LDS buffer (As, Bs)
   auto compute = [&](const LT* As, const LT* Bs) {
     if constexpr (X3) {
@@ -1228,6 +1261,10 @@ MG_DEV void gemm_tile(const AL& A, const BL& B, const EP& ep, int m0, int n0, in
         for (int i = 0; i < FM; ++i)
 #pragma unroll
           for (int j = 0; j < FN; ++j) acc[i][j] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bfv[j], acc[i][j], 0, 0, 0);
+        if constexpr (BG) {
+#pragma unroll
+          for (int i = 0; i < FM; ++i) bacc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(af[i], bias_b, bacc[i], 0, 0, 0);
+        }
       }
     } else {
 #pragma unroll
@@ -1409,6 +1446,19 @@ MG_DEV void gemm_tile(const AL& A, const BL& B, const EP& ep, int m0, int n0, in
     }
   }
 
+  if constexpr (BG) {
+    // every column of bacc[i] holds the sums of rows 4 * fq + r of A^T fragment i: column 0's lanes add them (an
+    // empty K range -- an empty group's slab block -- adds nothing)
+    if (bias_wave && kend > kbeg && fr == 0) {
+#pragma unroll
+      for (int i = 0; i < FM; ++i)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int m = m0 + wm * WM + i * 16 + fq * 4 + r;
+          if (m < Mloc) ep.bias_add(m, bacc[i][r]);
+        }
+    }
+  }
   epi_tile<BM, BN, EP, PF>(acc, smem, ep, m0, n0, Mloc, N, mrow_base);
 }
 

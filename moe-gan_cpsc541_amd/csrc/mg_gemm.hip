@@ -22,6 +22,18 @@ inline Grouping xcd_group() {  // XCD-aware block order (gemm_kernel): on unless
 
 inline bool a_xf(const mg_epilogue* e) { return e && (e->a_idx || e->a_rowscale || e->a_gelu); }
 
+// Bias gradients from the weight-gradient kernels' K loop (EpiBiasGrad, mg_gemm.h; the *_wgrad_bias entry points).
+// The separate column sums stay in deterministic mode (their fixed-order folds) and under tuning slot
+// MG_TUNE_WGRAD_BIAS_UNFUSED (A/B runs in one build).
+inline bool wgrad_bias_off() { return mg_det() || g_mg_tune[MG_TUNE_WGRAD_BIAS_UNFUSED] != 0; }
+template <typename TO>
+inline EpiBiasGrad<TO> with_bias_grad(const Epi<TO>& ep, float* bias_out, int64_t gstride) {
+  EpiBiasGrad<TO> b{ep};
+  b.bias_out = bias_out;
+  b.gstride_bo = gstride;
+  return b;
+}
+
 template <typename T, typename TO, int BM, int BN, bool AK, bool BKc, bool XF, bool X3 = false>
 void run_plain(int M, int N, int K, const void* A, int64_t lda, const void* B, int64_t ldb, void* C, int64_t ldc,
                const mg_epilogue* e, int splits, hipStream_t st) {
@@ -260,6 +272,50 @@ extern "C" int mg_gemm(int dtype, int M, int N, int K, const void* A, int64_t ld
     else run_plain_tiles<bf16_t, bf16_t>(a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, ep, splits, st);
   }
   return mg_check_launch("mg_gemm");
+}
+
+// Linear-layer weight gradient C[M][N] += alpha * sum_k A[k][m] B[k][n] (mg_gemm with a_kc = b_kc = 0, bf16 operands and
+// the plain atomic fp32 epilogue) that also leaves bias_out[m] += sum_k A[k][m]: the long-reduction kernel
+// (mg_wgrad_wide.hip) where mg_gemm would take it, else split-K tiles meeting in fp32 atomics as there.
+extern "C" int mg_gemm_wgrad_bias_fusable(int dtype) { return (!wgrad_bias_off() && dtype == MG_BF16) ? 1 : 0; }
+
+extern "C" int mg_gemm_wgrad_bias(int dtype, int M, int N, int K, const void* A, int64_t lda, const void* B,
+                                  int64_t ldb, float* C, int64_t ldc, float alpha, int splits, float* bias_out,
+                                  void* stream) {
+  MG_REQUIRE(bias_out, "bias_out must be set");
+  MG_REQUIRE(mg_gemm_wgrad_bias_fusable(dtype),
+             "not covered (deterministic mode / MG_TUNE_WGRAD_BIAS_UNFUSED / operands not bf16): run mg_gemm and mg_colsum");
+  MG_REQUIRE(M >= 0 && N >= 0 && K >= 0, "negative size");
+  if (M == 0 || N == 0) return MG_OK;
+  MG_REQUIRE(aligned16(A) && aligned16(B), "A/B must be 16-byte aligned");
+  MG_REQUIRE(M % 8 == 0 && N % 8 == 0 && lda % 8 == 0 && ldb % 8 == 0, "M/N/lda/ldb must be multiples of the 16-byte vector");
+  MG_REQUIRE(under2g((int64_t)K * lda, dtype) && under2g((int64_t)K * ldb, dtype) && under2g((int64_t)M * ldc, MG_F32),
+             "an operand exceeds 2 GiB (32-bit buffer offsets)");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  if (splits < 1 && mg_wgrad_wide(M, N, K, A, lda, B, ldb, C, ldc, alpha, st, bias_out))
+    return mg_check_launch("mg_gemm_wgrad_bias (wide weight gradient)");
+  if (splits < 1) {  // mg_gemm's rule for atomic epilogues
+    const int64_t tiles = (int64_t)cdiv(M, 64) * cdiv(N, 64);
+    const int target = g_mg_tune[MG_TUNE_ATOMIC_BLOCKS] > 0 ? (int)g_mg_tune[MG_TUNE_ATOMIC_BLOCKS] : 512;
+    const int64_t want = std::max<int64_t>(1, target / std::max<int64_t>(tiles, 1));
+    const int mink = g_mg_tune[MG_TUNE_ATOMIC_MINK] > 0 ? (int)g_mg_tune[MG_TUNE_ATOMIC_MINK] : 256;
+    splits = (int)std::max<int64_t>(1, std::min<int64_t>(want, K / mink));
+  }
+  if (K == 0) splits = 1;
+  mg_epilogue e{};
+  e.alpha = alpha;
+  e.atomic = 1;
+  auto ep = with_bias_grad(make_epi<float>(C, ldc, &e), bias_out, 0);
+  LdMC<bf16_t> la{reinterpret_cast<const bf16_t*>(A), lda, M, K, nullptr, 1, nullptr, 0};
+  LdMC<bf16_t> lb{reinterpret_cast<const bf16_t*>(B), ldb, N, K, nullptr, 1, nullptr, 0};
+  // run_plain_tiles' tile rule (its 128 x 256 tile is not built with the bias sum: 128^2 there)
+  const int tile = g_mg_tune[MG_TUNE_GEMM_TILE];
+  const bool small = tile == 0 && ((K <= Tile<bf16_t>::BK && g_mg_tune[MG_TUNE_SHORTK] != 2) || (K <= 256 && M >= 16384));
+  if (!small && (tile == 128 || tile == 257 || (tile == 0 && (int64_t)cdiv(M, 128) * cdiv(N, 128) * splits >= 480)))
+    launch_gemm<bf16_t, 128, 128, false, false>(la, lb, ep, M, N, K, splits, kNoGroup, 0, st);
+  else
+    launch_gemm<bf16_t, 64, 64, false, false>(la, lb, ep, M, N, K, splits, kNoGroup, 0, st);
+  return mg_check_launch("mg_gemm_wgrad_bias");
 }
 
 // ---------------------------------------------------------------------------
@@ -545,9 +601,10 @@ extern "C" int mg_conv2d_fwd(int dtype, const void* x, int B, int H, int W, int 
 }
 
 namespace {
-template <typename T, int BM, int BN, bool XF = false>
+// BG instantiations: bias_out[o] += sum over pixels of gy[:, o] from the same K loop (EpiBiasGrad)
+template <typename T, int BM, int BN, bool XF = false, bool BG = false>
 void run_wgrad(const void* gy, int64_t ldg, const void* x, int B, int H, int W, int Cin, const float* sc, int Cout,
-               int KH, int KW, int stride, int pad, float* gw, int splits, hipStream_t st) {
+               int KH, int KW, int stride, int pad, float* gw, int splits, hipStream_t st, float* bias_out = nullptr) {
   int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
   int P = B * OH * OW, N = KH * KW * Cin;
   LdMC<T> la{reinterpret_cast<const T*>(gy), ldg, Cout, P, nullptr, 1, nullptr, 0};
@@ -559,7 +616,8 @@ void run_wgrad(const void* gy, int64_t ldg, const void* x, int B, int H, int W, 
   e.remap_lgcin = ilog2(Cin);
   e.remap_taps = KH * KW;
   auto ep = make_epi<float>(gw, N, &e);
-  launch_gemm<T, BM, BN, false, false>(la, lb, ep, Cout, N, P, splits, kNoGroup, 0, st);
+  if constexpr (BG) launch_gemm<T, BM, BN, false, false>(la, lb, with_bias_grad(ep, bias_out, 0), Cout, N, P, splits, kNoGroup, 0, st);
+  else launch_gemm<T, BM, BN, false, false>(la, lb, ep, Cout, N, P, splits, kNoGroup, 0, st);
 }
 
 // Weight gradient with split-K into fp32 slabs written by the 8-column vector epilogue (coalesced, no atomics),
@@ -569,9 +627,10 @@ inline bool wgrad_s1(int H, int W, int KH, int KW, int stride, int pad, int tbk)
   return stride == 1 && KH == KW && 2 * pad == KH - 1 && W <= tbk && H <= 32 && pow2(H) && pow2(W);
 }
 
-template <typename T, int BM, int BN, bool XF = false>
+template <typename T, int BM, int BN, bool XF = false, bool BG = false>
 bool run_wgrad_slabs(const void* gy, int64_t ldg, const void* x, int B, int H, int W, int Cin, const float* sc,
-                     int Cout, int KH, int KW, int stride, int pad, float* gw, int splits, hipStream_t st) {
+                     int Cout, int KH, int KW, int stride, int pad, float* gw, int splits, hipStream_t st,
+                     float* bias_out = nullptr) {
   constexpr int TBK = tile_bk<T, false, BM, BN>();
   int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
   int P = B * OH * OW, N = KH * KW * Cin;
@@ -590,13 +649,17 @@ bool run_wgrad_slabs(const void* gy, int64_t ldg, const void* x, int B, int H, i
   slab.zstride = MN;
   slab.vec_ok = slab.host_vec_ok() ? 1 : 0;
   dim3 grid(cdiv(Cout, BM), cdiv(N, BN), splits);
+  using EPT = typename std::conditional<BG, EpiBiasGrad<float>, Epi<float>>::type;
+  EPT slab_ep;
+  if constexpr (BG) slab_ep = with_bias_grad(slab, bias_out, 0);
+  else slab_ep = slab;
   if (!XF && !g_mg_tune[MG_TUNE_S1_OFF] && wgrad_s1(H, W, KH, KW, stride, pad, TBK)) {
     LdMCConvS1<T> lb1{reinterpret_cast<const T*>(x), ilog2(Cin), ilog2(OW), OH, W, KW, pad, P, N};
-    hipLaunchKernelGGL((gemm_kernel<T, BM, BN, false, false, LdMC<T>, LdMCConvS1<T>, Epi<float>>), grid,
-                       dim3(NTHREADS), 0, st, la, lb1, slab, Cout, N, P, kchunk, xcd_group());
+    hipLaunchKernelGGL((gemm_kernel<T, BM, BN, false, false, LdMC<T>, LdMCConvS1<T>, EPT>), grid,
+                       dim3(NTHREADS), 0, st, la, lb1, slab_ep, Cout, N, P, kchunk, xcd_group());
   } else {
-    hipLaunchKernelGGL((gemm_kernel<T, BM, BN, false, false, LdMC<T>, LdMCConv<T, XF>, Epi<float>>), grid,
-                       dim3(NTHREADS), 0, st, la, lb, slab, Cout, N, P, kchunk, xcd_group());
+    hipLaunchKernelGGL((gemm_kernel<T, BM, BN, false, false, LdMC<T>, LdMCConv<T, XF>, EPT>), grid,
+                       dim3(NTHREADS), 0, st, la, lb, slab_ep, Cout, N, P, kchunk, xcd_group());
   }
   // (Cout x Cin / CC) blocks: enough to spread the slab reads over the chip, >= 8 channels per segment
   int lgCC = ilog2(Cin);
@@ -606,9 +669,59 @@ bool run_wgrad_slabs(const void* gy, int64_t ldg, const void* x, int B, int H, i
 }
 }  // namespace
 
+// ---------------------------------------------------------------------------
+// bias gradients from the weight-gradient kernels' K loop (EpiBiasGrad, mg_gemm.h)
+// ---------------------------------------------------------------------------
+namespace {
+// why mg_conv2d_wgrad_bias does not cover a call (nullptr: covered): the routes of mg_conv2d_wgrad that do not end
+// in a bf16 gemm_tile with a plain A loader
+const char* conv_wgrad_bias_refuse(int dtype, int H, int W, int Cin, const float* in_scale, int Cout, int KH, int KW,
+                                   int stride, int pad) {
+  if (wgrad_bias_off()) return "deterministic mode / MG_TUNE_WGRAD_BIAS_UNFUSED";
+  if (dtype != MG_BF16) return "bf16 operands only";
+  if (in_scale) return "modulated input (in_scale)";
+  if (KH == 1 && KW == 1 && stride == 1 && pad == 0) return "1x1 convs run the long-reduction kernel";
+  if (Cout == 32 && Cin >= 32 && mg_conv3_direct_ok(H, W, Cin, Cout, KH, KW, stride, pad, true))
+    return "the direct 32-channel 3x3 weight gradient";
+  const int tile = g_mg_tune[MG_TUNE_WGRAD_TILE];
+  if (tile == 256 || tile == 257) return "256-wide tiles are not built with the bias sum";
+  return nullptr;
+}
+
+int conv2d_wgrad_impl(int dtype, const void* gy, int64_t ldg, const void* x, int B, int H, int W, int Cin,
+                      const float* in_scale, int Cout, int KH, int KW, int stride, int pad, float* gw, int splits,
+                      float* bias_out, void* stream);
+}  // namespace
+
 extern "C" int mg_conv2d_wgrad(int dtype, const void* gy, int64_t ldg, const void* x, int B, int H, int W, int Cin,
                                const float* in_scale, int Cout, int KH, int KW, int stride, int pad, float* gw,
                                int splits, void* stream) {
+  return conv2d_wgrad_impl(dtype, gy, ldg, x, B, H, W, Cin, in_scale, Cout, KH, KW, stride, pad, gw, splits, nullptr,
+                           stream);
+}
+
+extern "C" int mg_conv2d_wgrad_bias_fusable(int dtype, int H, int W, int Cin, const float* in_scale, int Cout, int KH,
+                                            int KW, int stride, int pad) {
+  return conv_wgrad_bias_refuse(dtype, H, W, Cin, in_scale, Cout, KH, KW, stride, pad) ? 0 : 1;
+}
+
+extern "C" int mg_conv2d_wgrad_bias(int dtype, const void* gy, int64_t ldg, const void* x, int B, int H, int W,
+                                    int Cin, const float* in_scale, int Cout, int KH, int KW, int stride, int pad,
+                                    float* gw, int splits, float* bias_out, void* stream) {
+  MG_REQUIRE(bias_out, "bias_out must be set");
+  if (const char* why = conv_wgrad_bias_refuse(dtype, H, W, Cin, in_scale, Cout, KH, KW, stride, pad)) {
+    mg_set_error(std::string("mg_conv2d_wgrad_bias: not covered (") + why + "): run mg_conv2d_wgrad and mg_colsum");
+    return MG_ERR_ARG;
+  }
+  return conv2d_wgrad_impl(dtype, gy, ldg, x, B, H, W, Cin, in_scale, Cout, KH, KW, stride, pad, gw, splits, bias_out,
+                           stream);
+}
+
+namespace {
+// bias_out != nullptr: a call conv_wgrad_bias_refuse admits (bf16, the slab / atomic routes at the end)
+int conv2d_wgrad_impl(int dtype, const void* gy, int64_t ldg, const void* x, int B, int H, int W, int Cin,
+                      const float* in_scale, int Cout, int KH, int KW, int stride, int pad, float* gw, int splits,
+                      float* bias_out, void* stream) {
   MG_REQUIRE(dtype == MG_F32 || dtype == MG_BF16, "bad dtype");
   const int vec = dtype == MG_F32 ? 4 : 8;
   int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
@@ -685,6 +798,19 @@ extern "C" int mg_conv2d_wgrad(int dtype, const void* gy, int64_t ldg, const voi
     }
     return mg_check_launch("mg_conv2d_wgrad (scaled)");
   }
+  if (bias_out) {  // (bf16, no in_scale: the routes below with the bias sum in the K loop)
+    bool ok = false;
+    if (slabs)
+      ok = big ? run_wgrad_slabs<bf16_t, 128, 128, false, true>(gy, ldg, x, B, H, W, Cin, in_scale, Cout, KH, KW, stride,
+                                                                pad, gw, splits, st, bias_out)
+               : run_wgrad_slabs<bf16_t, 64, 64, false, true>(gy, ldg, x, B, H, W, Cin, in_scale, Cout, KH, KW, stride,
+                                                              pad, gw, splits, st, bias_out);
+    if (!ok) {
+      if (big) run_wgrad<bf16_t, 128, 128, false, true>(gy, ldg, x, B, H, W, Cin, in_scale, Cout, KH, KW, stride, pad, gw, splits, st, bias_out);
+      else run_wgrad<bf16_t, 64, 64, false, true>(gy, ldg, x, B, H, W, Cin, in_scale, Cout, KH, KW, stride, pad, gw, splits, st, bias_out);
+    }
+    return mg_check_launch("mg_conv2d_wgrad_bias");
+  }
   if (slabs && dtype == MG_BF16) {
     bool ok = big ? run_wgrad_slabs<bf16_t, 128, 128>(gy, ldg, x, B, H, W, Cin, in_scale, Cout, KH, KW, stride, pad,
                                                        gw, splits, st)
@@ -700,6 +826,7 @@ extern "C" int mg_conv2d_wgrad(int dtype, const void* gy, int64_t ldg, const voi
   else run_wgrad<bf16_t, 64, 64>(gy, ldg, x, B, H, W, Cin, in_scale, Cout, KH, KW, stride, pad, gw, splits, st);
   return mg_check_launch("mg_conv2d_wgrad");
 }
+}  // namespace
 
 // ---------------------------------------------------------------------------
 // grouped (per-expert) GEMMs
@@ -759,10 +886,11 @@ void run_grouped(int total_rows, int N, int K, int ngroups, const int32_t* row_o
   }
 }
 
-template <typename T, bool XF>
+// BG: bias_out[g][m] += sum over group g's rows of A[r][m] from the same K loop (EpiBiasGrad)
+template <typename T, bool XF, bool BG = false>
 void run_grouped_wgrad(int M, int N, int ngroups, const int32_t* row_off, int total_rows, const void* A, int64_t lda,
                        const void* B, int64_t ldb, const int32_t* b_idx, int b_idx_div, int b_gelu, float* C,
-                       int splits, const mg_epilogue* e, hipStream_t st) {
+                       int splits, const mg_epilogue* e, hipStream_t st, float* bias_out = nullptr) {
   LdMC<T, XF> la{reinterpret_cast<const T*>(A), lda, M, total_rows, e ? e->a_idx : nullptr,
              (e && e->a_idx_div > 0) ? e->a_idx_div : 1, e ? e->a_rowscale : nullptr, e ? e->a_gelu : 0};
   LdMC<T, XF> lb{reinterpret_cast<const T*>(B), ldb, N, total_rows, b_idx, b_idx_div > 0 ? b_idx_div : 1, nullptr,
@@ -788,10 +916,15 @@ void run_grouped_wgrad(int M, int N, int ngroups, const int32_t* row_off, int to
   ep.gstride_c = MN;
   if (slabs) ep.zstride = GMN;
   Grouping grp{2, ngroups, row_off, nullptr, 0};
-  if (sizeof(T) == 2 && M >= 128 && N >= 128 && g_mg_tune[MG_TUNE_GWGRAD_TILE] != 64)
-    launch_gemm<T, 128, 128, false, false, 1>(la, lb, ep, M, N, total_rows, splits, grp, 0, st);
-  else
-    launch_gemm<T, 64, 64, false, false, 1>(la, lb, ep, M, N, total_rows, splits, grp, 0, st);
+  const bool big = sizeof(T) == 2 && M >= 128 && N >= 128 && g_mg_tune[MG_TUNE_GWGRAD_TILE] != 64;
+  if constexpr (BG) {
+    auto epb = with_bias_grad(ep, bias_out, M);
+    if (big) launch_gemm<T, 128, 128, false, false, 1>(la, lb, epb, M, N, total_rows, splits, grp, 0, st);
+    else launch_gemm<T, 64, 64, false, false, 1>(la, lb, epb, M, N, total_rows, splits, grp, 0, st);
+  } else {
+    if (big) launch_gemm<T, 128, 128, false, false, 1>(la, lb, ep, M, N, total_rows, splits, grp, 0, st);
+    else launch_gemm<T, 64, 64, false, false, 1>(la, lb, ep, M, N, total_rows, splits, grp, 0, st);
+  }
   if (slabs)  // C[g][m][n] += alpha * sum_s slab[s][g][m][n]
     mg_fold_rows_submit(mg_fold_rows{slabs, GMN, splits, (int32_t)GMN, (int32_t)GMN, C, nullptr}, deferred, st);
 }
@@ -827,10 +960,50 @@ extern "C" int mg_gemm_grouped(int dtype, int total_rows, int N, int K, int ngro
   return mg_check_launch("mg_gemm_grouped");
 }
 
+namespace {
+int grouped_wgrad_impl(int dtype, int M, int N, int ngroups, const int32_t* row_off, int total_rows, const void* A,
+                       int64_t lda, const void* B, int64_t ldb, const int32_t* b_idx, int b_idx_div, int b_gelu,
+                       float* C, int splits, const mg_epilogue* ep, float* bias_out, void* stream);
+// why mg_gemm_grouped_wgrad_bias does not cover a call (nullptr: covered)
+const char* grouped_wgrad_bias_refuse(int dtype, const mg_epilogue* ep) {
+  if (wgrad_bias_off()) return "deterministic mode / MG_TUNE_WGRAD_BIAS_UNFUSED";
+  if (dtype != MG_BF16) return "bf16 operands only";
+  if (a_xf(ep)) return "a loader transform on A (a_idx / a_rowscale / a_gelu)";
+  return nullptr;
+}
+}  // namespace
+
 extern "C" int mg_gemm_grouped_wgrad(int dtype, int M, int N, int ngroups, const int32_t* row_off, int total_rows,
                                      const void* A, int64_t lda, const void* B, int64_t ldb, const int32_t* b_idx,
                                      int b_idx_div, int b_gelu, float* C, int splits, const mg_epilogue* ep,
                                      void* stream) {
+  return grouped_wgrad_impl(dtype, M, N, ngroups, row_off, total_rows, A, lda, B, ldb, b_idx, b_idx_div, b_gelu, C,
+                            splits, ep, nullptr, stream);
+}
+
+extern "C" int mg_gemm_grouped_wgrad_bias_fusable(int dtype, const mg_epilogue* ep) {
+  return grouped_wgrad_bias_refuse(dtype, ep) ? 0 : 1;
+}
+
+extern "C" int mg_gemm_grouped_wgrad_bias(int dtype, int M, int N, int ngroups, const int32_t* row_off,
+                                          int total_rows, const void* A, int64_t lda, const void* B, int64_t ldb,
+                                          const int32_t* b_idx, int b_idx_div, int b_gelu, float* C, int splits,
+                                          const mg_epilogue* ep, float* bias_out, void* stream) {
+  MG_REQUIRE(bias_out, "bias_out must be set");
+  if (const char* why = grouped_wgrad_bias_refuse(dtype, ep)) {
+    mg_set_error(std::string("mg_gemm_grouped_wgrad_bias: not covered (") + why +
+                 "): run mg_gemm_grouped_wgrad and mg_grouped_colsum");
+    return MG_ERR_ARG;
+  }
+  return grouped_wgrad_impl(dtype, M, N, ngroups, row_off, total_rows, A, lda, B, ldb, b_idx, b_idx_div, b_gelu, C,
+                            splits, ep, bias_out, stream);
+}
+
+namespace {
+// bias_out != nullptr: a call grouped_wgrad_bias_refuse admits
+int grouped_wgrad_impl(int dtype, int M, int N, int ngroups, const int32_t* row_off, int total_rows, const void* A,
+                       int64_t lda, const void* B, int64_t ldb, const int32_t* b_idx, int b_idx_div, int b_gelu,
+                       float* C, int splits, const mg_epilogue* ep, float* bias_out, void* stream) {
   MG_REQUIRE(dtype == MG_F32 || dtype == MG_BF16, "bad dtype");
   const int vec = dtype == MG_F32 ? 4 : 8;
   MG_REQUIRE(M % vec == 0 && N % vec == 0 && lda % vec == 0 && ldb % vec == 0, "M/N/lda/ldb must be vector multiples");
@@ -852,11 +1025,15 @@ extern "C" int mg_gemm_grouped_wgrad(int dtype, int M, int N, int ngroups, const
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   const bool xf = a_xf(ep) || b_idx || b_gelu;
 #define MG_GW(T, X) run_grouped_wgrad<T, X>(M, N, ngroups, row_off, total_rows, A, lda, B, ldb, b_idx, b_idx_div, b_gelu, C, splits, ep, st)
-  if (dtype == MG_F32) { if (xf) MG_GW(float, true); else MG_GW(float, false); }
+#define MG_GWB(X) run_grouped_wgrad<bf16_t, X, true>(M, N, ngroups, row_off, total_rows, A, lda, B, ldb, b_idx, b_idx_div, b_gelu, C, splits, ep, st, bias_out)
+  if (bias_out) { if (xf) MG_GWB(true); else MG_GWB(false); }  // (xf: a transform on B; A is plain)
+  else if (dtype == MG_F32) { if (xf) MG_GW(float, true); else MG_GW(float, false); }
   else { if (xf) MG_GW(bf16_t, true); else MG_GW(bf16_t, false); }
+#undef MG_GWB
 #undef MG_GW
   return mg_check_launch("mg_gemm_grouped_wgrad");
 }
+}  // namespace
 
 // ---------------------------------------------------------------------------
 // data gradient of a 4x4 / stride-2 / pad-1 conv (discriminator convs, R1 path)

@@ -58,10 +58,15 @@ MG_DEV bf16x8_t mc_frag(const bf16_t* img, int cols, int kbase, int c0, int lane
 // wave's DMA of step t, and one raw barrier per step publishes it (the pipeline rules of cdna_hip_programming.md
 // "Pipelining across barriers": all LDS in one array, no __syncthreads while a DMA is in flight).  Steps past the
 // split's rows read zeros (out-of-range offsets), so every step issues the same DMA count.
-template <int BM, int BN, int BK, int NB>
-__global__ __launch_bounds__(WT) void k_wgrad_wide(const bf16_t* __restrict__ A, int64_t lda,
-                                                   const bf16_t* __restrict__ B, int64_t ldb, int M, int N, int K,
-                                                   int kchunk, float* __restrict__ part) {
+//
+// BG (k_wgrad_wide_bias): also the bias gradient bias_out[m] += sum_k A[k][m].  Every A fragment is multiplied once
+// more, with a B fragment of bf16 ones in the waves that own the block's first column strip (wn == 0) of the blocks
+// of column tile 0 and of zeros elsewhere (no branch in the K step, as in gemm_tile; 1.0 * a is exact, the sum fp32);
+// every column of that accumulator holds the row sums, and column 0's lanes of the ones-waves add the block's partial
+// with one fp32 atomic per row.
+template <int BM, int BN, int BK, int NB, bool BG>
+MG_DEV void wgrad_wide_body(const bf16_t* __restrict__ A, int64_t lda, const bf16_t* __restrict__ B, int64_t ldb, int M,
+                            int N, int K, int kchunk, float* __restrict__ part, float* __restrict__ bias_out) {
   extern __shared__ __attribute__((aligned(16))) bf16_t dsm[];
   constexpr int AE = BK * BM, STAGE = BK * (BM + BN);
   constexpr int ARI = 512 / BM, BRI = 512 / BN;  // rows per 1-KiB DMA instruction
@@ -106,6 +111,15 @@ __global__ __launch_bounds__(WT) void k_wgrad_wide(const bf16_t* __restrict__ A,
   for (int a = 0; a < FM; ++a)
 #pragma unroll
     for (int b = 0; b < FN; ++b) acc[a][b] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  f32x4_t bacc[BG ? FM : 1];
+  const bool bias_wave = BG && blockIdx.y == 0 && wn == 0;
+  const bf16x8_t bias_b = __builtin_bit_cast(bf16x8_t, u16x8_t(bias_wave ? 0x3F80 : 0));
+  if constexpr (BG) {
+#pragma unroll
+    for (int a = 0; a < FM; ++a) bacc[a] = f32x4_t{0.f, 0.f, 0.f, 0.f};
+  }
+  (void)bacc;
+  (void)bias_b;
   const int nsteps = std::max(0, (k_hi - k_lo + BK - 1) / BK);
 #pragma unroll
   for (int p = 0; p < NB - 2; ++p) issue(p);
@@ -127,10 +141,22 @@ __global__ __launch_bounds__(WT) void k_wgrad_wide(const bf16_t* __restrict__ A,
 #pragma unroll
         for (int fn = 0; fn < FN; ++fn)
           acc[fm][fn] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, b[fn], acc[fm][fn], 0, 0, 0);
+        if constexpr (BG) bacc[fm] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a, bias_b, bacc[fm], 0, 0, 0);
       }
     }
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the zero-row DMAs past the last step land before the block ends
+  if constexpr (BG) {
+    if (bias_wave && (lane & 15) == 0) {
+#pragma unroll
+      for (int fm = 0; fm < FM; ++fm)
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int m = m0 + wm * WM + 16 * fm + 4 * (lane >> 4) + j;
+          if (m < M) atomicAdd(bias_out + m, bacc[fm][j]);
+        }
+    }
+  }
   // this block's partial tile, staged through the (now idle) LDS as [BM][BN] fp32 and stored in natural order as
   // 16-B row runs: part[split][m][n] (row pitch N), what the gradient-fold rows pass reads
   float* pb = part + (int64_t)blockIdx.z * M * N;
@@ -162,6 +188,20 @@ __global__ __launch_bounds__(WT) void k_wgrad_wide(const bf16_t* __restrict__ A,
           if (m < M && n < N) pb[(int64_t)m * N + n] = acc[fm][fn][j];
         }
   }
+}
+
+template <int BM, int BN, int BK, int NB>
+__global__ __launch_bounds__(WT) void k_wgrad_wide(const bf16_t* __restrict__ A, int64_t lda,
+                                                   const bf16_t* __restrict__ B, int64_t ldb, int M, int N, int K,
+                                                   int kchunk, float* __restrict__ part) {
+  wgrad_wide_body<BM, BN, BK, NB, false>(A, lda, B, ldb, M, N, K, kchunk, part, nullptr);
+}
+template <int BM, int BN, int BK, int NB>
+__global__ __launch_bounds__(WT) void k_wgrad_wide_bias(const bf16_t* __restrict__ A, int64_t lda,
+                                                        const bf16_t* __restrict__ B, int64_t ldb, int M, int N, int K,
+                                                        int kchunk, float* __restrict__ part,
+                                                        float* __restrict__ bias_out) {
+  wgrad_wide_body<BM, BN, BK, NB, true>(A, lda, B, ldb, M, N, K, kchunk, part, bias_out);
 }
 
 // immediate fold (a scaled or strided C): level 1 tmp[grp][i] = sum of part[s][i] over the group's splits
@@ -197,8 +237,18 @@ __global__ __launch_bounds__(256) void k_wide_final(const float* __restrict__ tm
 
 template <int BM, int BN, int BK, int NB>
 void launch_wide(dim3 grid, hipStream_t st, const bf16_t* a, int64_t lda, const bf16_t* b, int64_t ldb, int M, int N,
-                 int K, int kchunk, float* part) {
+                 int K, int kchunk, float* part, float* bias_out) {
   constexpr int bytes = NB * BK * (BM + BN) * 2;
+  if (bias_out) {
+    static bool attr_b = [] {
+      return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wgrad_wide_bias<BM, BN, BK, NB>),
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
+    }();
+    (void)attr_b;
+    hipLaunchKernelGGL((k_wgrad_wide_bias<BM, BN, BK, NB>), grid, dim3(WT), bytes, st, a, lda, b, ldb, M, N, K, kchunk,
+                       part, bias_out);
+    return;
+  }
   static bool attr = [] {
     return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_wgrad_wide<BM, BN, BK, NB>),
                                hipFuncAttributeMaxDynamicSharedMemorySize, bytes) == hipSuccess;
@@ -211,9 +261,9 @@ void launch_wide(dim3 grid, hipStream_t st, const bf16_t* a, int64_t lda, const 
 
 // Called by mg_gemm for bf16, a_kc = b_kc = 0 (both operands [K][*] row-major), an fp32 C accumulated through a
 // plain atomic epilogue (alpha only), and by mg_conv2d_wgrad for 1x1 / stride-1 convolutions.  Returns true when it
-// handled the call.
+// handled the call.  bias_out != nullptr: bias_out[m] += sum_k A[k][m] from the same K loop (k_wgrad_wide_bias).
 bool mg_wgrad_wide(int M, int N, int K, const void* A, int64_t lda, const void* B, int64_t ldb, float* C, int64_t ldc,
-                   float alpha, hipStream_t st) {
+                   float alpha, hipStream_t st, float* bias_out) {
   const int mode = g_mg_tune[MG_TUNE_WIDE_WGRAD];
   if (mode == 1) return false;  // A/B: the generic split-K GEMM
   if (K < 2048 || M % 8 || N % 8 || (int64_t)M * N > 1024 * 1024) return false;
@@ -245,8 +295,8 @@ bool mg_wgrad_wide(int M, int N, int K, const void* A, int64_t lda, const void* 
     bool deferred = false;
     float* part = mg_fold_partials((size_t)splits * MN * sizeof(float), st, &deferred);
     if (!part) return false;
-    if (big) launch_wide<256, 256, 32, 4>(grid, st, a, lda, b, ldb, M, N, K, kchunk, part);
-    else launch_wide<128, 128, 32, 8>(grid, st, a, lda, b, ldb, M, N, K, kchunk, part);
+    if (big) launch_wide<256, 256, 32, 4>(grid, st, a, lda, b, ldb, M, N, K, kchunk, part, bias_out);
+    else launch_wide<128, 128, 32, 8>(grid, st, a, lda, b, ldb, M, N, K, kchunk, part, bias_out);
     mg_fold_rows_submit(mg_fold_rows{part, MN, (int32_t)splits, (int32_t)MN, (int32_t)MN, C, nullptr}, deferred, st);
     return true;
   }
@@ -254,8 +304,8 @@ bool mg_wgrad_wide(int M, int N, int K, const void* A, int64_t lda, const void* 
   float* part = reinterpret_cast<float*>(mg_workspace((size_t)(splits + ngrp) * MN * sizeof(float), st));
   if (!part) return false;
   float* tmp = part + (size_t)splits * MN;
-  if (big) launch_wide<256, 256, 32, 4>(grid, st, a, lda, b, ldb, M, N, K, kchunk, part);
-  else launch_wide<128, 128, 32, 8>(grid, st, a, lda, b, ldb, M, N, K, kchunk, part);
+  if (big) launch_wide<256, 256, 32, 4>(grid, st, a, lda, b, ldb, M, N, K, kchunk, part, bias_out);
+  else launch_wide<128, 128, 32, 8>(grid, st, a, lda, b, ldb, M, N, K, kchunk, part, bias_out);
   hipLaunchKernelGGL(k_wide_fold, dim3(cdiv(MN, 1024), ngrp), dim3(256), 0, st, part, splits, MN, per, tmp);
   hipLaunchKernelGGL(k_wide_final, dim3(cdiv(MN, 256)), dim3(256), 0, st, tmp, ngrp, M, N, alpha, C, ldc);
   return true;

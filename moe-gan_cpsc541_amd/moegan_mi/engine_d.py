@@ -125,27 +125,29 @@ class DiscriminatorEngine:
         g_a1, _ = self._head_bwd(g_img_part, g_img_part.shape[1], f["h1"], B, Hf, want_params)
         if want_params:
             dW1, gb1 = self.dW["conv_layers.2."], self.G("conv_layers.2.bias")
-            self.side.run(lambda: (ops.conv2d_wgrad(g_a1, f["h0"], 256, 4, 4, 2, 1, dW1),
-                                   ops.colsum(g_a1.view(-1, 256), gb1, defer=True)), g_a1, f["h0"])
+            # (the bias gradient rides in the weight gradient's K loop where the library covers it, ops.conv2d_wgrad)
+            self.side.run(lambda: ops.conv2d_wgrad(g_a1, f["h0"], 256, 4, 4, 2, 1, dW1, bias_grad=gb1), g_a1, f["h0"])
         g_a0 = torch.empty(B, H // 2, H // 2, 128, device=self.dev, dtype=self.cdt)
         ops.dgrad_s2(g_a1, self.W1cls, 128, g_a0, ep=E_(act=MUL_LRELU_GRAD, aux=f["h0"], ld_aux=128))
         if want_params:
             dW0, gb0 = self.dW["conv_layers.0."].view(128, 48), self.G("conv_layers.0.bias")
-            self.side.run(lambda: (self._d0_wgrad(f["cols"], g_a0, dW0),
-                                   ops.colsum(g_a0.view(-1, 128), gb0, defer=True)), g_a0, f["cols"])
+            self.side.run(lambda: self._d0_wgrad(f["cols"], g_a0, dW0, gb0), g_a0, f["cols"])
         if g_input is not None:
             self._d0_dgrad(g_a0, g_input)
         return g_a1, g_a0
 
-    def _d0_wgrad(self, cols, g, dW0):
-        """dW0 [128, 48] += conv_layers.0 weight gradient; ``cols`` is the im2col matrix, or (image, strides)."""
+    def _d0_wgrad(self, cols, g, dW0, gb0=None):
+        """dW0 [128, 48] += conv_layers.0 weight gradient; ``cols`` is the im2col matrix, or (image, strides).
+        gb0 [128] += the bias gradient (column sums of g)."""
         if isinstance(cols, tuple):
             img, strides = cols
             B, OH, OW, _ = g.shape
-            ops.d0_wgrad(img, strides, B, 2 * OH, 2 * OW, g, dW0)
+            ops.d0_wgrad(img, strides, B, 2 * OH, 2 * OW, g, dW0, bias_grad=gb0)
         else:
             ops.gemm(g.view(-1, 128), cols, 128, 48, g.numel() // 128, a_kc=False, b_kc=False, out=dW0,
                      ep=E_(atomic=1), splits=0)
+            if gb0 is not None:
+                ops.colsum(g.view(-1, 128), gb0, defer=True)
 
     def _d0_dgrad(self, g, out):
         if self._d0_ok(2 * g.shape[1]):

@@ -593,17 +593,20 @@ class GeneratorEngine:
             # expert layer 2: dH = gG @ W2_e, times GELU'(pre)
             ops.gemm_grouped(gG, sv["W2"], row_off, tile_off, sv["max_tiles"], Hd, C, b_kc=False, b_gstride=C * Hd,
                              out=gP, ldb=Hd, ep=E_(act=MUL_GELU_GRAD, aux=Pre, ld_aux=Hd))
+        # unfused blocks: the bias gradients ride in the weight gradients' K loops where the library covers it, else
+        # ops.gemm_grouped_wgrad runs the grouped column sum
+        bg2 = None if fused else gb2
         if Hid is not None:
-            gw2 = lambda: ops.gemm_grouped_wgrad(gG, Hid, row_off, n, C, Hd, gW2)  # noqa: E731
+            gw2 = lambda: ops.gemm_grouped_wgrad(gG, Hid, row_off, n, C, Hd, gW2, bias_grad=bg2)  # noqa: E731
         else:  # GELU(Pre) formed by the B loader (the forward kept only the pre-activation)
-            gw2 = lambda: ops.gemm_grouped_wgrad(gG, Pre, row_off, n, C, Hd, gW2, b_gelu=1)  # noqa: E731
-        self.side.run(lambda: (gw2(), None if fused else ops.grouped_colsum(gG, row_off, C, n, gb2)), gG)
+            gw2 = lambda: ops.gemm_grouped_wgrad(gG, Pre, row_off, n, C, Hd, gW2, b_gelu=1, bias_grad=bg2)  # noqa: E731
+        self.side.run(gw2, gG)
         # expert layer 1
         if not fused:
             ops.gemm_grouped(gP, sv["W1"], row_off, tile_off, sv["max_tiles"], C, Hd, b_kc=False, b_gstride=Hd * C,
                              out=gX, ldb=C)
-        self.side.run(lambda: (ops.gemm_grouped_wgrad(gP, sv["Xg"], row_off, n, Hd, C, gW1),
-                               None if fused else ops.grouped_colsum(gP, row_off, Hd, n, gb1)), gP)
+        self.side.run(lambda: ops.gemm_grouped_wgrad(gP, sv["Xg"], row_off, n, Hd, C, gW1,
+                                                     bias_grad=None if fused else gb1), gP)
         if self.on_grad_final is not None:  # this block's expert parameters receive no further gradient
             ops.fold_flush()  # (a weight-gradient fold deferred on this stream lands before the bucket's all-reduce)
             lo = self.st.offsets[ex + "0.net.0.weight"][0]
@@ -698,7 +701,7 @@ class GeneratorEngine:
         g_qkv = ops.attn_bwd(sv["qkv"], sv["att"], g_att, sv["lse"], B, L_, C)
         g_n1 = ops.linear_dgrad(g_qkv, self.Pc(pre + "self_attn.in_proj_weight"))
         gWqkv, gbqkv = self.G(pre + "self_attn.in_proj_weight"), self.G(pre + "self_attn.in_proj_bias")
-        self.side.run(lambda: (ops.linear_wgrad(g_qkv, sv["n1"], gWqkv), ops.colsum(g_qkv, gbqkv, defer=True)), g_qkv)
+        self.side.run(lambda: ops.linear_wgrad(g_qkv, sv["n1"], gWqkv, bias_grad=gbqkv), g_qkv)
         g_xf0 = g_xf1
         ops.layernorm_bwd(g_n1, sv["xf0"], sv["mu1"], sv["rs1"], self.P(pre + "norm1.weight"), g_xf0,
                           self.G(pre + "norm1.weight"), self.G(pre + "norm1.bias"), accumulate=1)
@@ -790,8 +793,8 @@ class GeneratorEngine:
                           self.G(pre + "norm3.weight"), self.G(pre + "norm3.bias"), accumulate=1)
         # cross-attention: out_proj -> softmax(q k^T) v -> q projection -> LN2 (query side)
         g_o = ops.linear_dgrad(g_xf1, self.Pc(pre + "cross_attn.out_proj.weight"))
-        ops.linear_wgrad(g_xf1, sv["o"], self.G(pre + "cross_attn.out_proj.weight"))
-        ops.colsum(g_xf1, self.G(pre + "cross_attn.out_proj.bias"))  # (at once: g_xf1 is accumulated into below)
+        ops.linear_wgrad(g_xf1, sv["o"], self.G(pre + "cross_attn.out_proj.weight"),  # (the bias sum at once, not
+                         bias_grad=self.G(pre + "cross_attn.out_proj.bias"), defer=False)  # deferred: g_xf1 is accumulated into below)
         if sv["rag"] is None:
             g_q, g_kv = ops.xattn_bwd(sv["q"], sv["kv"], sv["o"], g_o, sv["lse2"], B, L_, Lk, C,
                                       key_len=sv["key_len"])
@@ -800,8 +803,7 @@ class GeneratorEngine:
                                              C)
         gWi, gbi = self.G(pre + "cross_attn.in_proj_weight"), self.G(pre + "cross_attn.in_proj_bias")
         g_n2 = ops.linear_dgrad(g_q, self.Pc(pre + "cross_attn.in_proj_weight")[:C])
-        ops.linear_wgrad(g_q, sv["n2"], gWi[:C])
-        ops.colsum(g_q, gbi[:C])
+        ops.linear_wgrad(g_q, sv["n2"], gWi[:C], bias_grad=gbi[:C], defer=False)
         g_xfs = g_xf1  # residual path, accumulate LN2 backward into it
         ops.layernorm_bwd(g_n2, sv["xf_s"], sv["mu2"], sv["rs2"], self.P(pre + "norm2.weight"), g_xfs,
                           self.G(pre + "norm2.weight"), self.G(pre + "norm2.bias"), accumulate=1)
@@ -816,12 +818,12 @@ class GeneratorEngine:
                          accumulate=1)
         # self-attention
         g_att = ops.linear_dgrad(g_xfs, self.Pc(pre + "self_attn.out_proj.weight"))
-        ops.linear_wgrad(g_xfs, sv["att"], self.G(pre + "self_attn.out_proj.weight"))
-        ops.colsum(g_xfs, self.G(pre + "self_attn.out_proj.bias"))
+        ops.linear_wgrad(g_xfs, sv["att"], self.G(pre + "self_attn.out_proj.weight"),
+                         bias_grad=self.G(pre + "self_attn.out_proj.bias"), defer=False)
         g_qkv = ops.attn_bwd(sv["qkv"], sv["att"], g_att, sv["lse"], B, L_, C)
         g_n1 = ops.linear_dgrad(g_qkv, self.Pc(pre + "self_attn.in_proj_weight"))
         gWqkv, gbqkv = self.G(pre + "self_attn.in_proj_weight"), self.G(pre + "self_attn.in_proj_bias")
-        self.side.run(lambda: (ops.linear_wgrad(g_qkv, sv["n1"], gWqkv), ops.colsum(g_qkv, gbqkv, defer=True)), g_qkv)
+        self.side.run(lambda: ops.linear_wgrad(g_qkv, sv["n1"], gWqkv, bias_grad=gbqkv), g_qkv)
         g_xf0 = g_xfs
         ops.layernorm_bwd(g_n1, sv["xf0"], sv["mu1"], sv["rs1"], self.P(pre + "norm1.weight"), g_xf0,
                           self.G(pre + "norm1.weight"), self.G(pre + "norm1.bias"), accumulate=1)

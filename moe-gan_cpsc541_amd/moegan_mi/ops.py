@@ -246,12 +246,21 @@ def linear_dgrad(g, W, out=None, accumulate=0, out_dtype=None, lrelu_out=None, q
     return gemm(g, W, M, K, N, b_kc=False, out=out, out_dtype=out_dtype, ep=ep)
 
 
-def linear_wgrad(g, x, gW, alpha=1.0):
-    """gW [N,K] (fp32) += g^T x for g [M,N], x [M,K]."""
+def linear_wgrad(g, x, gW, alpha=1.0, bias_grad=None, defer=True):
+    """gW [N,K] (fp32) += g^T x for g [M,N], x [M,K].  ``bias_grad`` [N] fp32 += column sums of g: from the weight
+    gradient's own K loop where the library covers the call (mg_gemm_wgrad_bias_fusable), else by the column sum
+    (``defer``: queued on COLSUMS inside a step)."""
     M, N = g.shape
     K = x.shape[1]
-    return gemm(g, x, N, K, M, a_kc=False, b_kc=False, out=gW, ldc=gW.stride(0),
-                ep=E(alpha=alpha, atomic=1), splits=0)
+    if bias_grad is not None and _gdt(g) == L.MG_BF16 and x.dtype == g.dtype and L.lib().mg_gemm_wgrad_bias_fusable(
+            L.MG_BF16):
+        call("mg_gemm_wgrad_bias", L.MG_BF16, N, K, M, ptr(g), _ld(g), ptr(x), _ld(x), ptr(gW), gW.stride(0), alpha, 0,
+             ptr(bias_grad), S())
+        return gW
+    gemm(g, x, N, K, M, a_kc=False, b_kc=False, out=gW, ldc=gW.stride(0), ep=E(alpha=alpha, atomic=1), splits=0)
+    if bias_grad is not None:
+        colsum(g, bias_grad, defer=defer)
+    return gW
 
 
 def conv2d(x, wpack, Cout, KH, KW, stride=1, pad=0, in_scale=None, out=None, out_dtype=None, ep=None, ldy=None,
@@ -311,11 +320,24 @@ def conv2d_mx8(xq, xsc, wq, wsc, Cout, KH, KW, stride=1, pad=0, out=None, out_dt
     return out
 
 
-def conv2d_wgrad(gy, x, Cout, KH, KW, stride, pad, gw, in_scale=None, ldg=None, splits=0):
-    """gw [Cout,Cin,KH,KW] fp32 += weight gradient (mg_conv2d_wgrad)."""
+TUNE_WGRAD_BIAS_UNFUSED = 30  # mg_common.h MG_TUNE_WGRAD_BIAS_UNFUSED: 1 keeps the bias gradients on the column sums
+
+
+def conv2d_wgrad(gy, x, Cout, KH, KW, stride, pad, gw, in_scale=None, ldg=None, splits=0, bias_grad=None):
+    """gw [Cout,Cin,KH,KW] fp32 += weight gradient (mg_conv2d_wgrad).  ``bias_grad`` [Cout] fp32 += column sums of
+    gy: from the weight gradient's own K loop where the library covers the call (mg_conv2d_wgrad_bias_fusable),
+    else by the (deferred) column sum."""
     B, H, W, Cin = x.shape
-    call("mg_conv2d_wgrad", dt(x), ptr(gy), ldg or gy.shape[-1], ptr(x), B, H, W, Cin, ptr(in_scale), Cout, KH, KW,
+    ldg = ldg or gy.shape[-1]
+    if bias_grad is not None and L.lib().mg_conv2d_wgrad_bias_fusable(dt(x), H, W, Cin, ptr(in_scale), Cout, KH, KW,
+                                                                      stride, pad):
+        call("mg_conv2d_wgrad_bias", dt(x), ptr(gy), ldg, ptr(x), B, H, W, Cin, ptr(in_scale), Cout, KH, KW, stride,
+             pad, ptr(gw), splits, ptr(bias_grad), S())
+        return gw
+    call("mg_conv2d_wgrad", dt(x), ptr(gy), ldg, ptr(x), B, H, W, Cin, ptr(in_scale), Cout, KH, KW,
          stride, pad, ptr(gw), splits, S())
+    if bias_grad is not None:
+        colsum(gy.view(-1, gy.shape[-1]), bias_grad, C=Cout, ld=ldg, defer=True)
     return gw
 
 
@@ -387,10 +409,19 @@ def ffn_bwd_fusable(dtype, C):
 
 
 def gemm_grouped_wgrad(A, B, row_off, total_rows, M, N, out, *, b_idx=None, b_idx_div=1, b_gelu=0, ep=None,
-                       lda=None, ldb=None, splits=0):
-    """out[g] (fp32 [G,M,N]) += sum over rows of group g of A[r,:]^T B[r,:]."""
+                       lda=None, ldb=None, splits=0, bias_grad=None):
+    """out[g] (fp32 [G,M,N]) += sum over rows of group g of A[r,:]^T B[r,:].  ``bias_grad`` (fp32 [G,M]) += the
+    groups' column sums of A: from the same K loop where the library covers the call
+    (mg_gemm_grouped_wgrad_bias_fusable), else by grouped_colsum."""
+    if bias_grad is not None and L.lib().mg_gemm_grouped_wgrad_bias_fusable(dt(A), ep):
+        call("mg_gemm_grouped_wgrad_bias", dt(A), M, N, row_off.shape[0] - 1, ptr(row_off), total_rows, ptr(A),
+             lda or _ld(A), ptr(B), ldb or _ld(B), ptr(b_idx), b_idx_div, b_gelu, ptr(out), splits, ep,
+             ptr(bias_grad), S())
+        return out
     call("mg_gemm_grouped_wgrad", dt(A), M, N, row_off.shape[0] - 1, ptr(row_off), total_rows, ptr(A),
          lda or _ld(A), ptr(B), ldb or _ld(B), ptr(b_idx), b_idx_div, b_gelu, ptr(out), splits, ep, S())
+    if bias_grad is not None:
+        grouped_colsum(A, row_off, M, total_rows, bias_grad)
     return out
 
 
@@ -1086,10 +1117,17 @@ def d0_fwd(x, strides, B, H, W, w0p, bias=None, aux=None):
     return out
 
 
-def d0_wgrad(x, strides, B, H, W, g, dw):
-    """dw [128, 48] fp32 (GEMM layout) += weight gradient of conv_layers.0 for output gradient g [B, H/2, W/2, 128]."""
+def d0_wgrad(x, strides, B, H, W, g, dw, bias_grad=None):
+    """dw [128, 48] fp32 (GEMM layout) += weight gradient of conv_layers.0 for output gradient g [B, H/2, W/2, 128].
+    ``bias_grad`` [128] fp32 += column sums of g: from the same kernel where the library says so
+    (mg_d0_wgrad_bias_fusable), else by the (deferred) column sum."""
     sb, sh, sw, sc = strides
+    if bias_grad is not None and L.lib().mg_d0_wgrad_bias_fusable():
+        call("mg_d0_wgrad_bias", dt(x), ptr(x), sb, sh, sw, sc, B, H, W, ptr(g), ptr(dw), ptr(bias_grad), S())
+        return dw
     call("mg_d0_wgrad", dt(x), ptr(x), sb, sh, sw, sc, B, H, W, ptr(g), ptr(dw), S())
+    if bias_grad is not None:
+        colsum(g.view(-1, 128), bias_grad, defer=True)
     return dw
 
 

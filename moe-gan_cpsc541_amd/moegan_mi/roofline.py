@@ -24,9 +24,10 @@ FAMILIES = {
     "conv_fwd": ("mfma", ("mg_conv2d_fwd",)),
     "conv_fwd_mx8": ("mfma8", ("mg_conv2d_fwd_mx8",)),  # MX-fp8 (C5): priced against the fp8 MFMA peak
     "conv_dgrad_s2": ("mfma", ("mg_conv2d_dgrad_s2",)),
-    "conv_wgrad+fold": ("mfma", ("mg_conv2d_wgrad",)),
-    "expert_gemm": ("mfma", ("mg_gemm_grouped", "mg_gemm_grouped_wgrad", "mg_moe_ffn_fwd", "mg_moe_ffn_bwd")),
-    "gemm": ("mfma", ("mg_gemm", "mg_gemm_batch")),
+    "conv_wgrad+fold": ("mfma", ("mg_conv2d_wgrad", "mg_conv2d_wgrad_bias")),
+    "expert_gemm": ("mfma", ("mg_gemm_grouped", "mg_gemm_grouped_wgrad", "mg_gemm_grouped_wgrad_bias",
+                             "mg_moe_ffn_fwd", "mg_moe_ffn_bwd")),
+    "gemm": ("mfma", ("mg_gemm", "mg_gemm_wgrad_bias", "mg_gemm_batch")),
     "attention": ("mfma", ("mg_attn_fwd", "mg_attn_bwd", "mg_xattn_fwd", "mg_xattn_bwd", "mg_xattn_ragged_fwd",
                           "mg_xattn_ragged_bwd")),
     "router_fwd": ("hbm", ("mg_router_fwd",)),
@@ -49,7 +50,7 @@ FAMILIES = {
     "im2col_col2im": ("hbm", ("mg_im2col_4x4s2", "mg_col2im_4x4s2")),
     # deferred second passes of the two-pass gradient reductions (mg_fold.hip), one batched launch per kind
     "grad_fold": ("hbm", ("mg_fold_flush", "mg_fold_rows_batch", "mg_fold_rows_queue", "mg_fold_defer")),
-    "d_conv0": ("hbm", ("mg_d0_fwd", "mg_d0_wgrad", "mg_d0_dgrad")),
+    "d_conv0": ("hbm", ("mg_d0_fwd", "mg_d0_wgrad", "mg_d0_wgrad_bias", "mg_d0_dgrad")),
     "elementwise": ("hbm", ("mg_cast", "mg_copy2d", "mg_lrelu_mask_mul", "mg_upsample2x_fwd", "mg_upsample2x_bwd",
                             "mg_const_fwd", "mg_gated_axpy", "mg_select_if", "mg_zero_if", "mg_clip_patches",
                             "mg_clip_patches_bwd")),
@@ -115,19 +116,19 @@ def _conv_out(H, W, KH, KW, s, p):
 
 def work(name, a):
     """Algorithmic work of one call: FLOPs (MFMA families) or bytes (HBM families); None = not modelled."""
-    if name in ("mg_conv2d_fwd", "mg_conv2d_wgrad", "mg_conv2d_fwd_mx8"):
+    if name in ("mg_conv2d_fwd", "mg_conv2d_wgrad", "mg_conv2d_wgrad_bias", "mg_conv2d_fwd_mx8"):
         OH, OW = _conv_out(a["H"], a["W"], a["KH"], a["KW"], a["stride"], a["pad"])
         return 2.0 * a["B"] * OH * OW * a["Cout"] * a["KH"] * a["KW"] * a["Cin"]
     if name == "mg_conv2d_dgrad_s2":  # 4x4 stride-2 transpose: every input pixel takes 4 of the 16 taps
         return 2.0 * a["B"] * (2 * a["OH"]) * (2 * a["OW"]) * a["Cin"] * a["Cg"] * 4
-    if name == "mg_gemm":
+    if name in ("mg_gemm", "mg_gemm_wgrad_bias"):
         return 2.0 * a["M"] * a["N"] * a["K"]
     if name == "mg_gemm_batch":
         d = a["descs"]
         return sum(2.0 * d[i].M * d[i].N * d[i].K for i in range(a["n"]))
     if name == "mg_gemm_grouped":
         return 2.0 * a["total_rows"] * a["N"] * a["K"]
-    if name == "mg_gemm_grouped_wgrad":
+    if name in ("mg_gemm_grouped_wgrad", "mg_gemm_grouped_wgrad_bias"):
         return 2.0 * a["M"] * a["N"] * a["total_rows"]
     if name == "mg_moe_ffn_fwd":  # two GEMMs per routed row
         return 4.0 * a["total_rows"] * a["C"] * a["Hd"]
@@ -266,10 +267,11 @@ def work(name, a):
     if name == "mg_col2im_4x4s2":
         B, OH, OW, C = a["B"], a["OH"], a["OW"], a["C"]
         return B * OH * OW * 16 * C * ELT[a["in_dtype"]] + B * 4 * OH * OW * C * ELT[a["out_dtype"]]
-    if name in ("mg_d0_fwd", "mg_d0_wgrad"):  # image read + the 128-channel bf16 map (out / aux / gradient)
+    if name in ("mg_d0_fwd", "mg_d0_wgrad", "mg_d0_wgrad_bias"):  # image read + the 128-channel bf16 map (out / aux / gradient)
         B, H, W = a["B"], a["H"], a["W"]
         maps = 1 + (1 if name == "mg_d0_fwd" and a["aux"] else 0)
-        return B * H * W * 3 * ELT[a["in_dtype"]] + maps * B * (H // 2) * (W // 2) * 128 * 2
+        extra = 128 * 4 if name == "mg_d0_wgrad_bias" else 0  # the bias gradient row
+        return B * H * W * 3 * ELT[a["in_dtype"]] + maps * B * (H // 2) * (W // 2) * 128 * 2 + extra
     if name == "mg_d0_dgrad":
         B, OH, OW = a["B"], a["OH"], a["OW"]
         return B * OH * OW * 128 * 2 + B * 4 * OH * OW * 3 * ELT[a["out_dtype"]]
@@ -353,14 +355,16 @@ def alg_bytes(name, a):
         e = ELT[a["dtype"]]
         return (a["B"] * a["H"] * a["W"] * a["Cin"] * e + a["Cout"] * a["KH"] * a["KW"] * a["Cin"] * e +
                 a["B"] * OH * OW * a["Cout"] * ELT[a["y_dtype"]])
-    if name == "mg_conv2d_wgrad":
+    if name in ("mg_conv2d_wgrad", "mg_conv2d_wgrad_bias"):
         OH, OW = _conv_out(a["H"], a["W"], a["KH"], a["KW"], a["stride"], a["pad"])
         e = ELT[a["dtype"]]
         return (a["B"] * OH * OW * a["Cout"] * e + a["B"] * a["H"] * a["W"] * a["Cin"] * e +
-                a["Cout"] * a["Cin"] * a["KH"] * a["KW"] * 4)
+                a["Cout"] * a["Cin"] * a["KH"] * a["KW"] * 4 + (a["Cout"] * 4 if name.endswith("_bias") else 0))
     if name == "mg_gemm":
         e = ELT[a["dtype"]]
         return (a["M"] * a["K"] + a["K"] * a["N"]) * e + a["M"] * a["N"] * ELT[a["c_dtype"]]
+    if name == "mg_gemm_wgrad_bias":  # fp32 C and the bias gradient row
+        return (a["M"] * a["K"] + a["K"] * a["N"]) * ELT[a["dtype"]] + a["M"] * a["N"] * 4 + a["M"] * 4
     if name == "mg_gemm_grouped":
         e = ELT[a["dtype"]]
         return (a["total_rows"] * a["K"] + a["ngroups"] * a["N"] * a["K"]) * e + a["total_rows"] * a["N"] * ELT[a["c_dtype"]]
