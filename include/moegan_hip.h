@@ -714,6 +714,32 @@ int mg_const_fwd(int dtype, const float* cst, int C, int HW, int B, void* out, v
 /* gconst[c][p] += sum_b g[b][p][c]. */
 int mg_const_bwd(int dtype, const void* g, int C, int HW, int B, float* gc, void* stream);
 
+/* ---- evaluation metrics over feature rows (csrc/mg_eval.hip; no reference counterpart: the reference measures
+   validation losses only, t2i_moe_gan.py:1519-1639) ----
+   Both entry points take fp32 feature rows: 16-byte aligned base and pitch (ld % 4 == 0, ld >= d), d % 4 == 0,
+   4 <= d <= 1024, at most 2^20 rows.  Dot products run on the f32-input MFMA (v_mfma_f32_32x32x2_f32): every dot is
+   one fp32 fma chain over k in a fixed order that depends on d alone, so equal rows give bitwise-equal dots.  A
+   violated precondition returns MG_ERR_ARG and launches nothing. */
+
+/* Sums of the cubic kernel k(a, b) = (gamma <a, b> + coef0)^3 (fp32 from the fp32 dot; summed in fp64) over
+   X [n, d] and Y [m, d], n, m >= 2:
+     sums[0] = sum_{i != j} k(x_i, x_j)   sums[1] = sum_{i != j} k(y_i, y_j)   sums[2] = sum_{i, j} k(x_i, y_j)
+   (the unbiased MMD^2 / KID is sums[0] / (n (n - 1)) + sums[1] / (m (m - 1)) - 2 sums[2] / (n m)).  The work is
+   cut into 64 x 64 tiles -- the upper triangle of the two symmetric products (off-diagonal tiles counted twice)
+   and all of the cross product; each tile's block stores one fp64 partial into `partials`, and a second launch
+   folds them in a fixed order: no atomics, bitwise repeatable.  `partials` is caller-owned device memory of
+   npartials >= tx (tx + 1) / 2 + ty (ty + 1) / 2 + tx ty doubles, tx = ceil(n / 64), ty = ceil(m / 64); no other
+   memory is used. */
+int mg_poly_mmd_sums(const float* X, int64_t ldx, int n, const float* Y, int64_t ldy, int m, int d, float gamma,
+                     float coef0, double* partials, int64_t npartials, double* sums, void* stream);
+
+/* Retrieval ranks inside consecutive groups of `group` rows (1 <= group <= 128; the last group may be shorter) of
+   image features I [n, d] and text features T [n, d], n >= 1, with s_ij = <I_i, T_j> (no normalisation here):
+     diag[i] = s_ii        rank[i] = #{j in group(i), j != i: s_ij > s_ii} + #{j in group(i), j < i: s_ij == s_ii}
+   One block per group; rank == 0 means row i's own text is its best match (ties go to the lower index). */
+int mg_retrieval_rank(const float* I, int64_t ldi, const float* T, int64_t ldt, int n, int d, int group,
+                      int32_t* rank, float* diag, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,72 @@
+"""Checkpoint + validation set -> KID / CLIP score / R-precision over CLIP image features, as one JSON object.
+
+This build's extension (the reference has no evaluation entry point).  The metrics are those of
+moegan_mi/evaluate.py: the generator draws one image per validation caption in eval mode; real and generated images
+go through the image tower of ``--clip_weights``; ``kid_clip`` compares the two feature sets, ``clip_score`` and
+``r_precision`` compare each generated image with its caption's pooled embedding.
+
+  python evaluate_model.py --checkpoint CK --val_images IMAGES.npy --val_embeddings TEXT.npy --clip_weights W
+                           [--ema] [--num_samples N] [--truncation_psi P] [--seed S] [--group G] [--batch_size B]
+                           [--num_experts E --topk K --dtype fp32|bf16 --max_resolution R]
+
+Prints {"kid_clip": ..., "clip_score": ..., "r_precision": ..., "r_precision_n": ..., "n": ...}; r_precision is NaN
+when fewer than ``--group`` samples were evaluated.  The checkpoint may be any of the shapes generate_images.py takes.
+"""
+import argparse
+import json
+import os
+import sys
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+
+
+def parse_args(argv=None):
+    p = argparse.ArgumentParser(description="Evaluate an Aurora GAN-MoE checkpoint over CLIP features (MI355X)")
+    p.add_argument("--checkpoint", type=str, required=True, help="Path to checkpoint file")
+    p.add_argument("--val_images", type=str, required=True, help=".npy of validation images [N, 3, H, W] in [-1, 1]")
+    p.add_argument("--val_embeddings", type=str, required=True, help=".npy of their pooled text embeddings [N, 512]")
+    p.add_argument("--clip_weights", type=str, required=True,
+                   help="local OpenAI CLIP state_dict / safetensors with the image tower")
+    p.add_argument("--ema", action="store_true",
+                   help="evaluate the averaged generator ('generator_ema'); falls back to 'generator' with a warning")
+    p.add_argument("--num_samples", type=int, default=None, help="evaluate at most this many samples (default: all)")
+    p.add_argument("--truncation_psi", type=float, default=1.0)
+    p.add_argument("--seed", type=int, default=0, help="seed of the latent draws")
+    p.add_argument("--group", type=int, default=100, help="R-precision: captions per retrieval group (1 to 128)")
+    p.add_argument("--batch_size", type=int, default=64)
+    p.add_argument("--num_experts", type=int, default=4)
+    p.add_argument("--topk", type=int, default=None, help="sparse top-k routing (default: dense soft combine)")
+    p.add_argument("--dtype", choices=["fp32", "bf16"], default="fp32")
+    p.add_argument("--max_resolution", type=int, default=16, choices=[16, 32, 64, 128])
+    args = p.parse_args(argv)
+    if not 1 <= args.group <= 128:
+        p.error("--group must be between 1 and 128")
+    if args.num_samples is not None and args.num_samples < 2:
+        p.error("--num_samples must be at least 2")
+    return args
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    import t2i_moe_gan as M
+    from generate_images import generator_state
+    from torch.utils.data import DataLoader
+    from train_model import ProcessedMSCOCODataset
+    device = M.DEVICE
+    ck = torch.load(args.checkpoint, map_location="cpu", weights_only=True)
+    generator = M.AuroraGenerator(max_resolution=args.max_resolution, num_experts=args.num_experts, topk=args.topk,
+                                  dtype=args.dtype).to(device)
+    generator.load_state_dict(generator_state(ck, args.ema))
+    M.load_clip_weights(args.clip_weights, device)
+    loader = DataLoader(ProcessedMSCOCODataset(args.val_images, args.val_embeddings), batch_size=args.batch_size,
+                        shuffle=False)
+    m = M.evaluate_aurora_gan(generator, loader, num_samples=args.num_samples, truncation_psi=args.truncation_psi,
+                              seed=args.seed, group=args.group)
+    print(json.dumps(m))
+    return m
+
+
+if __name__ == "__main__":
+    main()

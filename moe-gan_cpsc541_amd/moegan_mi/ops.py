@@ -1254,3 +1254,53 @@ def r1(g, B, gamma, r1_out, u):
 def lrelu_mask_mul(a, m, out):
     call("mg_lrelu_mask_mul", dt(a), ptr(a), dt(m), ptr(m), a.numel(), dt(out), ptr(out), S())
     return out
+
+
+MMD_TILE = 64  # mg_poly_mmd_sums tile edge (include/moegan_hip.h): sizes the caller-owned partials buffer
+
+
+def _feature_rows(t, what):
+    """fp32 [rows, d] with unit column stride and 16-byte aligned rows, as the evaluation kernels read them."""
+    if t.dim() != 2 or t.dtype != torch.float32 or not t.is_cuda:
+        raise L.MGError(f"{what}: expected a 2-D fp32 device tensor, got {tuple(t.shape)} {t.dtype} {t.device}")
+    if t.stride(1) != 1 or t.stride(0) % 4 or t.data_ptr() % 16:
+        t = t.contiguous()
+    return t
+
+
+def mmd_partials(n, m):
+    """Doubles mg_poly_mmd_sums needs in its partials buffer: one per 64 x 64 tile it visits."""
+    tx, ty = -(-n // MMD_TILE), -(-m // MMD_TILE)
+    return tx * (tx + 1) // 2 + ty * (ty + 1) // 2 + tx * ty
+
+
+def poly_mmd_sums(X, Y, gamma, coef0=1.0, partials=None):
+    """float64 [3] = (sum_{i != j} k(x_i, x_j), sum_{i != j} k(y_i, y_j), sum_{i, j} k(x_i, y_j)) of the cubic kernel
+    k(a, b) = (gamma <a, b> + coef0)^3 over fp32 rows X [n, d], Y [m, d] (mg_poly_mmd_sums: exact-fp32 MFMA dots,
+    fp64 fixed-order reduction; bitwise repeatable, O(tiles) extra memory)."""
+    X, Y = _feature_rows(X, "X"), _feature_rows(Y, "Y")
+    n, d = X.shape
+    m = Y.shape[0]
+    if Y.shape[1] != d:
+        raise L.MGError(f"poly_mmd_sums: X has {d} columns, Y {Y.shape[1]}")
+    need = mmd_partials(max(n, 2), max(m, 2))
+    if partials is None:
+        partials = torch.empty(need, device=X.device, dtype=torch.float64)
+    sums = torch.empty(3, device=X.device, dtype=torch.float64)
+    call("mg_poly_mmd_sums", ptr(X), X.stride(0), n, ptr(Y), Y.stride(0), m, d, float(gamma), float(coef0),
+         ptr(partials), partials.numel(), ptr(sums), S())
+    return sums
+
+
+def retrieval_rank(I, T, group):
+    """(rank int32 [n], diag fp32 [n]) of image rows I [n, d] against text rows T [n, d] inside consecutive groups of
+    ``group`` rows (mg_retrieval_rank): diag[i] = <I_i, T_i>, rank[i] = the number of texts of row i's group that beat
+    its own (ties to the lower index).  No normalisation here."""
+    I, T = _feature_rows(I, "I"), _feature_rows(T, "T")
+    n, d = I.shape
+    if tuple(T.shape) != (n, d):
+        raise L.MGError(f"retrieval_rank: I is {tuple(I.shape)}, T {tuple(T.shape)}")
+    rank = torch.empty(n, device=I.device, dtype=torch.int32)
+    diag = torch.empty(n, device=I.device, dtype=torch.float32)
+    call("mg_retrieval_rank", ptr(I), I.stride(0), ptr(T), T.stride(0), n, d, int(group), ptr(rank), ptr(diag), S())
+    return rank, diag

@@ -609,7 +609,7 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
                      max_resolution=16, *, clip_weight_64=None, clip_weight_32=None, num_experts=NUM_EXPERTS,
                      topk=None, dtype=None, process_group=None, seed=0, resume_from=None, save_every_epoch=False,
                      use_graphs=True, on_batch_done=None, text_tokens=False, max_text_tokens=None, clip_grad=False,
-                     ema_kimg=None, ema_rampup=0.05):
+                     ema_kimg=None, ema_rampup=0.05, eval_every=None, eval_samples=None, eval_truncation_psi=1.0):
     """Reference :1029-1669.  ``clip_weight_64``/``clip_weight_32`` (the names train_model.py passes,
     SURVEY.md §0) map to the 16x16 / 8x8 CLIP weights.  ``use_amp`` selects bf16 (the MI355X mixed
     precision; the reference's fp16 GradScaler is not needed) unless ``dtype`` is given.
@@ -640,6 +640,11 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
     half-life at that fraction of the optimizer steps taken so far (0 / None: constant).  The average is advanced
     inside the generator's optimizer launch (StepConfig.ema_halflife), sampled with ``generator.ema_generator()``
     / ``sample_aurora_gan(use_ema=True)`` and saved as ``generator_ema``; validation stays on the live generator.
+    ``eval_every`` (this build's extension; None / 0 = off, the loop as it was): every that many epochs, after the
+    validation pass, ``evaluate_aurora_gan`` runs on the validation loader -- on the moving average when one is kept,
+    else on the live generator -- with at most ``eval_samples`` samples at ``eval_truncation_psi``, and
+    ``val_kid_clip`` / ``val_clip_score`` / ``val_r_precision`` / ``val_eval_images`` join the dict
+    ``metric_callback`` receives.  It needs ``val_dataloader`` and the build's image tower (load_clip_weights).
     ``resume_from``: a resume checkpoint (:1484-1491 layout, ours or the reference's) to start from;
     ``save_every_epoch``: write that layout after every epoch (the reference's commented-out :1642-1652).
 
@@ -673,6 +678,15 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
         if not ema_kimg > 0:
             raise ValueError(f"ema_kimg must be positive, got {ema_kimg}")
         ema_halflife = ema_kimg * 1000.0 / (int(bs) * acc * world)
+    eval_every = int(eval_every) if eval_every else 0
+    if eval_every < 0:
+        raise ValueError(f"eval_every must be a positive number of epochs, got {eval_every}")
+    if eval_every:
+        from moegan_mi.step import clip_tower
+        if val_dataloader is None:
+            raise ValueError("eval_every needs a val_dataloader: the evaluation runs on the validation set")
+        if clip_tower(_clip_model) is None:
+            raise ValueError("eval_every needs the build's CLIP image tower: call load_clip_weights(path) first")
     # max_resolution 16 is the reference generator; 32 / 64 / 128 train the progressive extension (layout.py)
     if clip_grad and _clip_model is None:
         raise RuntimeError("clip_grad=True needs the CLIP image tower: call load_clip_weights(path) first")
@@ -786,6 +800,16 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
         if val_dataloader is not None:
             vm = _validate(generator, discriminator, val_dataloader, gan_loss, temperature_factor, eff_kl, device,
                            process_group, g_local)
+            if eval_every and (epoch + 1) % eval_every == 0:
+                from moegan_mi.evaluate import format_metrics
+                em = evaluate_aurora_gan(generator, val_dataloader, num_samples=eval_samples,
+                                         truncation_psi=eval_truncation_psi, seed=seed,
+                                         use_ema=generator._store.ema is not None, process_group=process_group)
+                vm.update(val_kid_clip=em["kid_clip"], val_clip_score=em["clip_score"],
+                          val_r_precision=em["r_precision"], val_eval_images=em["n"])
+                if rank == 0:
+                    print(f"Evaluation ({'EMA' if generator._store.ema is not None else 'live'} generator) - "
+                          f"{format_metrics(em)}")
             stop = False
             if rank == 0:
                 print(f"Validation Results - D_loss: {vm['val_d_loss']:.4f}, G_loss: {vm['val_g_loss']:.4f}, "
@@ -859,6 +883,19 @@ def _validate(generator, discriminator, loader, gan_loss, temperature_factor, ef
     vm = {k: float(tot[i]) / n for i, k in enumerate(keys)}
     vm["val_clip_loss"] = vm["val_clip_loss_16"]
     return vm
+
+
+def evaluate_aurora_gan(generator, dataloader, **kw):
+    """KID / CLIP score / R-precision of ``generator`` over the registered image tower's features
+    (moegan_mi.evaluate.evaluate_generator; its keywords: num_samples, truncation_psi, seed, use_ema, group,
+    process_group, return_features).  This build's extension; needs load_clip_weights."""
+    from moegan_mi.evaluate import evaluate_generator
+    from moegan_mi.step import clip_tower
+    tower = clip_tower(_clip_model)
+    if tower is None:
+        raise RuntimeError("evaluate_aurora_gan needs the build's CLIP image tower: call load_clip_weights(path) "
+                           "first (a foreign model registered through set_clip_model has no encode_generated)")
+    return evaluate_generator(generator, dataloader, tower, **kw)
 
 
 def sample_aurora_gan(generator, text_prompt, num_samples=1, truncation_psi=0.7, device=DEVICE, text_tokens=None,

@@ -104,9 +104,19 @@ def parse_args(argv=None):
                         "images (StyleGAN's convention); saved as 'generator_ema' (default: off)")
     p.add_argument("--ema_rampup", type=float, default=0.05,
                    help="with --ema_kimg: cap the half-life at this fraction of the steps taken so far (0: none)")
+    p.add_argument("--eval_every", type=int, default=None,
+                   help="every N epochs, after validation: KID / CLIP score / R-precision of the validation set over "
+                        "the CLIP image tower's features (the averaged generator when --ema_kimg keeps one); needs "
+                        "--clip_weights and validation data (default: off)")
+    p.add_argument("--eval_samples", type=int, default=None,
+                   help="with --eval_every: evaluate at most M validation samples (default: all)")
+    p.add_argument("--eval_truncation_psi", type=float, default=1.0,
+                   help="with --eval_every: truncation psi of the evaluated samples")
     args = p.parse_args(argv)
     if args.clip_grad and not args.clip_weights:
         p.error("--clip_grad needs --clip_weights (the CLIP image tower whose backward it runs)")
+    if args.eval_every and not args.clip_weights:
+        p.error("--eval_every needs --clip_weights (the CLIP image tower whose features it compares)")
     return args
 
 
@@ -185,6 +195,11 @@ def main(argv=None):
     if args.ema_kimg is not None:
         kw.setdefault("ema_kimg", args.ema_kimg)
         kw.setdefault("ema_rampup", args.ema_rampup)
+    if args.eval_every:
+        kw.setdefault("eval_every", args.eval_every)
+        kw.setdefault("eval_samples", args.eval_samples)
+    if kw.get("eval_every"):
+        kw.setdefault("eval_truncation_psi", args.eval_truncation_psi)
     G, D = M.train_aurora_gan(train_dl, val_dataloader=val_dl, device=device, save_dir=args.save_dir,
                               num_experts=args.num_experts, topk=args.topk, dtype=args.dtype, process_group=pg,
                               resume_from=args.resume, save_every_epoch=args.save_every_epoch, **kw)
