@@ -716,7 +716,7 @@ int mg_const_bwd(int dtype, const void* g, int C, int HW, int B, float* gc, void
 
 /* ---- evaluation metrics over feature rows (csrc/mg_eval.hip; no reference counterpart: the reference measures
    validation losses only, t2i_moe_gan.py:1519-1639) ----
-   Both entry points take fp32 feature rows: 16-byte aligned base and pitch (ld % 4 == 0, ld >= d), d % 4 == 0,
+   Every entry point takes fp32 feature rows: 16-byte aligned base and pitch (ld % 4 == 0, ld >= d), d % 4 == 0,
    4 <= d <= 1024, at most 2^20 rows.  Dot products run on the f32-input MFMA (v_mfma_f32_32x32x2_f32): every dot is
    one fp32 fma chain over k in a fixed order that depends on d alone, so equal rows give bitwise-equal dots.  A
    violated precondition returns MG_ERR_ARG and launches nothing. */
@@ -739,6 +739,29 @@ int mg_poly_mmd_sums(const float* X, int64_t ldx, int n, const float* Y, int64_t
    One block per group; rank == 0 means row i's own text is its best match (ties go to the lower index). */
 int mg_retrieval_rank(const float* I, int64_t ldi, const float* T, int64_t ldt, int n, int d, int group,
                       int32_t* rank, float* diag, void* stream);
+
+/* The two primitives of improved precision / recall and density / coverage (moegan_mi/evaluate.py prdc).  Squared
+   distances are fp64, D(a, b) = (sq_a + sq_b) - 2 dot(a, b): sq_x is the row's squared norm summed in fp64 from the
+   fp32 entries, dot the fp32 MFMA dot above; D is never clamped and no square root is taken.  Both walk 64 x 64
+   tiles, a block owning 64 rows and one of S segments of the column tiles, and a second launch folds the segments
+   in a fixed order: no n x m buffer, no atomics, bitwise repeatable.  For `rows` rows against `cols` columns
+     S(rows, cols) = max(1, min(ceil(cols / 64), 8, ceil(512 / ceil(rows / 64)))). */
+
+/* sq[i] = the squared norm of row i and radius2[i] = the k-th smallest of {D(x_i, x_j) : j != i} over X [n, d],
+   2 <= n, 1 <= k <= 16, k < n.  Self is left out by index, so a duplicate row is a neighbour at distance 0; the
+   result is an order statistic of a multiset and needs no tie rule.  `work` is caller-owned device memory of
+   nwork >= n k S(n, n) doubles (each row's k smallest per segment); no other memory is used. */
+int mg_knn_radius2(const float* X, int64_t ldx, int n, int d, int k, double* work, int64_t nwork, double* sq,
+                   double* radius2, void* stream);
+
+/* For each row a of A [na, d] against B [nb, d] (1 <= na, nb), given the squared norms of both sets and B's radii
+   (mg_knn_radius2):
+     count[a] = #{b : D(a, b) <= radius2B[b]}        dmin2[a] = min_b D(a, b)
+   `work` is caller-owned device memory of nwork >= 2 na S(na, nb) doubles (a count and a minimum per row and
+   segment); no other memory is used. */
+int mg_manifold_counts(const float* A, int64_t lda, int na, const double* sqA, const float* B, int64_t ldb, int nb,
+                       const double* sqB, const double* radius2B, int d, double* work, int64_t nwork, int32_t* count,
+                       double* dmin2, void* stream);
 
 #ifdef __cplusplus
 }

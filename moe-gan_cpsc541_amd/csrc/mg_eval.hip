@@ -220,8 +220,251 @@ __global__ __launch_bounds__(256) void k_retrieval_rank(const float* __restrict_
   }
 }
 
+// ---- precision / recall / density / coverage: k-th-nearest-neighbour radii and manifold-membership counts ----
+// Both walk 64 x 64 tiles of a product of two row sets like k_poly_mmd_tiles (same staging, same MFMA chain), but a
+// block owns a strip of 64 rows and one of S segments of the column tiles (grid = strips x S), and what it keeps
+// per row -- a sorted list of k squared distances, or a count and a minimum -- goes to the caller's `work` buffer
+// for a second launch to fold across the segments.  Squared distances are fp64: (sq_a + sq_b) - 2 dot, the dot
+// being the fp32 MFMA dot (2 dot is exact, so two fp64 roundings); never clamped, no square root.
+
+constexpr int kDP = kTile + 1;     // pitch of the transposed dot tile (odd: the accumulator stores spread over banks)
+constexpr int kMaxK = 16;          // nearest_k <= 16
+constexpr int kMaxSplits = 8;      // column segments per launch <= 8
+constexpr int kSplitBlocks = 512;  // ... and no more than bring the grid to about this many blocks
+
+// column segments of a launch with `strips` row strips over `tiles` column tiles (the header documents it: the
+// caller sizes `work` by it)
+int col_splits(int strips, int tiles) { return std::max(1, std::min({tiles, kMaxSplits, cdiv(kSplitBlocks, strips)})); }
+
+// acc = this wave's 32 x 32 quadrant of A[arow0 ..] B[brow0 ..]^T over all of d, chunk by chunk as in
+// k_poly_mmd_tiles; every thread of the block calls it, and it ends on a barrier
+MG_DEV void tile_dots(const float* __restrict__ A, int64_t lda, int64_t arow0, int na, const float* __restrict__ B,
+                      int64_t ldb, int64_t brow0, int nb, int d, float (*As)[kLDP], float (*Bs)[kLDP], int ar, int br,
+                      int h, f32x16_t& acc) {
+#pragma unroll
+  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
+  Stage<kTile> sa, sb;
+  sa.load(A, lda, arow0, na, 0, d);
+  sb.load(B, ldb, brow0, nb, 0, d);
+  for (int k0 = 0; k0 < d; k0 += kKC) {
+    sa.store(As);
+    sb.store(Bs);
+    __syncthreads();
+    if (k0 + kKC < d) {
+      sa.load(A, lda, arow0, na, k0 + kKC, d);
+      sb.load(B, ldb, brow0, nb, k0 + kKC, d);
+    }
+    mma_chunk(As, Bs, ar, br, h, acc);
+    __syncthreads();
+  }
+}
+
+// The k smallest of the multiset get(0 .. N), ascending, to put(slot, value): round by round the smallest value
+// above the last one and how often it occurs (+inf fills what the multiset cannot: NaN entries are never taken).
+// The result depends on the multiset alone, not on the order of its entries.
+template <class Get, class Put>
+MG_DEV void k_smallest(Get get, int N, int k, Put put) {
+  const double inf = __builtin_huge_val();
+  double cur = -inf;
+  int out = 0;
+  while (out < k) {
+    double m = inf;
+    int c = 0;
+    for (int i = 0; i < N; ++i) {
+      const double v = get(i);
+      if (v > cur) {
+        if (v < m) {
+          m = v;
+          c = 1;
+        } else if (v == m) {
+          ++c;
+        }
+      }
+    }
+    if (c == 0) break;
+    for (; c > 0 && out < k; --c) put(out++, m);
+    cur = m;
+  }
+  for (; out < k; ++out) put(out, inf);
+}
+
+// sq[row] = sum_k X[row][k]^2 in fp64: one wave per row, lane l takes the 16-B vectors l, l + 64, ..., then a fixed
+// xor tree
+__global__ __launch_bounds__(256) void k_row_sq(const float* __restrict__ X, int64_t ld, int n, int d,
+                                                double* __restrict__ sq) {
+  const int64_t row = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const int lane = threadIdx.x & 63;
+  double s = 0.0;
+  if (row < n) {  // (wave-uniform)
+    for (int k = 4 * lane; k < d; k += 256) {
+      const f32x4_t v = *reinterpret_cast<const f32x4_t*>(X + row * ld + k);
+#pragma unroll
+      for (int j = 0; j < 4; ++j) s += (double)v[j] * (double)v[j];
+    }
+  }
+  s = wave_sum_f64(s);
+  if (row < n && lane == 0) sq[row] = s;
+}
+
+// Block (strip, seg): rows [64 strip, 64 strip + 64) of X against the column tiles [seg tps, (seg + 1) tps) of X.
+// After a tile's MFMA chain the dots go through LDS (over the staging buffers), transposed, to the scan: thread
+// (row = t & 63, q = t >> 6) takes the tile's columns 16 q .. 16 q + 15 of its row and keeps the k smallest
+// distances it has seen, ascending, in lists[q][slot][row] (LDS, private to the thread until the end); an element
+// is inserted only when it is below the list's k-th value, which after the first tiles few are.  Self is left out
+// by index.  At the end the thread with q == 0 merges its row's four lists into work[(row S + seg) k + slot].
+__global__ __launch_bounds__(256) void k_knn_tiles(const float* __restrict__ X, int64_t ldx, int n, int d, int k,
+                                                   const double* __restrict__ sq, int tiles, int tps, int S,
+                                                   double* __restrict__ work) {
+  __shared__ __attribute__((aligned(16))) float stage[2 * kTile * kLDP];
+  float(*As)[kLDP] = reinterpret_cast<float(*)[kLDP]>(stage);
+  float(*Bs)[kLDP] = As + kTile;
+  float(*dotT)[kDP] = reinterpret_cast<float(*)[kDP]>(stage);  // [column][row], over the staged tiles between chains
+  static_assert(kTile * kDP <= 2 * kTile * kLDP, "the dot tile must fit the staging buffers");
+  extern __shared__ double lists[];  // [4][k][64]
+  const double inf = __builtin_huge_val();
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+  const int wr = w >> 1, wc = w & 1;
+  const int seg = blockIdx.y;
+  const int64_t arow0 = (int64_t)blockIdx.x * kTile;
+  const int srow = lane, q = w;
+  const int64_t grow = arow0 + srow;
+  double* L = lists + (q * k) * kTile + srow;  // slot s at L[s * kTile]
+  for (int s = 0; s < k; ++s) L[s * kTile] = inf;
+  __syncthreads();  // (a segment without tiles goes straight to the merge)
+  double thr = inf;
+  const double sqa = grow < n ? sq[grow] : 0.0;
+
+  const int t1 = std::min(tiles, (seg + 1) * tps);
+  for (int t = seg * tps; t < t1; ++t) {
+    const int64_t brow0 = (int64_t)t * kTile;
+    f32x16_t acc;
+    tile_dots(X, ldx, arow0, n, X, ldx, brow0, n, d, As, Bs, wr * 32 + r, wc * 32 + r, h, acc);
+    // (tile_dots ended on a barrier: the staged tiles are free)
+#pragma unroll
+    for (int reg = 0; reg < 16; ++reg) dotT[wc * 32 + r][wr * 32 + acc_row(reg, h)] = acc[reg];
+    __syncthreads();
+    if (grow < n) {
+      for (int c = 0; c < 16; ++c) {
+        const int64_t col = brow0 + q * 16 + c;  // (wave-uniform)
+        if (col >= n) break;
+        if (col == grow) continue;
+        const double D = (sqa + sq[col]) - 2.0 * (double)dotT[q * 16 + c][srow];
+        if (D < thr) {
+          int s = k - 1;
+          while (s > 0 && L[(s - 1) * kTile] > D) {
+            L[s * kTile] = L[(s - 1) * kTile];
+            --s;
+          }
+          L[s * kTile] = D;
+          thr = L[(k - 1) * kTile];
+        }
+      }
+    }
+    __syncthreads();  // the next chain stages over the dot tile
+  }
+  if (q == 0 && grow < n) {
+    double* out = work + (grow * S + seg) * k;
+    k_smallest([&](int i) { return lists[i * kTile + srow]; }, 4 * k, k, [&](int s, double v) { out[s] = v; });
+  }
+}
+
+// radius2[row] = the k-th smallest of the row's S segment lists (thread per row)
+__global__ __launch_bounds__(256) void k_knn_fold(const double* __restrict__ work, int n, int k, int S,
+                                                  double* __restrict__ radius2) {
+  const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (row >= n) return;
+  const double* in = work + row * S * k;
+  double kth = 0.0;
+  k_smallest([&](int i) { return in[i]; }, S * k, k, [&](int s, double v) {
+    if (s == k - 1) kth = v;
+  });
+  radius2[row] = kth;
+}
+
+// Block (strip, seg): rows [64 strip, ...) of A against the column tiles [seg tps, (seg + 1) tps) of B.  A lane's
+// accumulators are 16 rows of one column, so it keeps a count (D <= radius2B[column]) and a minimum of D per
+// accumulator register over all its tiles; at the end the 32 lanes that share a row fold theirs, then the two waves
+// that do.  work[(2 seg) na + row] = the count (as a double), work[(2 seg + 1) na + row] = the minimum (+inf for a
+// segment without columns).
+__global__ __launch_bounds__(256) void k_manifold_tiles(const float* __restrict__ A, int64_t lda, int na,
+                                                        const double* __restrict__ sqA, const float* __restrict__ B,
+                                                        int64_t ldb, int nb, const double* __restrict__ sqB,
+                                                        const double* __restrict__ r2B, int d, int tiles, int tps,
+                                                        double* __restrict__ work) {
+  __shared__ float As[kTile][kLDP], Bs[kTile][kLDP];
+  __shared__ double sA[kTile], redm[2][kTile];
+  __shared__ int redc[2][kTile];
+  const double inf = __builtin_huge_val();
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 31, h = lane >> 5;
+  const int wr = w >> 1, wc = w & 1;
+  const int seg = blockIdx.y;
+  const int64_t arow0 = (int64_t)blockIdx.x * kTile;
+  if (threadIdx.x < kTile) sA[threadIdx.x] = arow0 + threadIdx.x < na ? sqA[arow0 + threadIdx.x] : 0.0;
+  __syncthreads();
+
+  int cnt[16];
+  double mn[16];
+#pragma unroll
+  for (int reg = 0; reg < 16; ++reg) cnt[reg] = 0, mn[reg] = inf;
+  const int t1 = std::min(tiles, (seg + 1) * tps);
+  for (int t = seg * tps; t < t1; ++t) {
+    const int64_t brow0 = (int64_t)t * kTile;
+    const int64_t gj = brow0 + wc * 32 + r;
+    const bool valid = gj < nb;
+    const double sb = valid ? sqB[gj] : 0.0, rb = valid ? r2B[gj] : 0.0;
+    f32x16_t acc;
+    tile_dots(A, lda, arow0, na, B, ldb, brow0, nb, d, As, Bs, wr * 32 + r, wc * 32 + r, h, acc);
+    if (valid) {
+#pragma unroll
+      for (int reg = 0; reg < 16; ++reg) {
+        const double D = (sA[wr * 32 + acc_row(reg, h)] + sb) - 2.0 * (double)acc[reg];
+        cnt[reg] += D <= rb ? 1 : 0;
+        mn[reg] = D < mn[reg] ? D : mn[reg];
+      }
+    }
+  }
+#pragma unroll
+  for (int reg = 0; reg < 16; ++reg) {
+    int c = cnt[reg];
+    double m = mn[reg];
+#pragma unroll
+    for (int o = 16; o > 0; o >>= 1) {  // the 32 lanes of this lane half share the row
+      c += __shfl_xor(c, o, 64);
+      const double mo = __shfl_xor(m, o, 64);
+      m = mo < m ? mo : m;
+    }
+    if (r == 0) {
+      redc[wc][wr * 32 + acc_row(reg, h)] = c;
+      redm[wc][wr * 32 + acc_row(reg, h)] = m;
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x < kTile && arow0 + threadIdx.x < na) {
+    const int i = threadIdx.x;
+    work[(int64_t)(2 * seg) * na + arow0 + i] = (double)(redc[0][i] + redc[1][i]);
+    work[(int64_t)(2 * seg + 1) * na + arow0 + i] = redm[1][i] < redm[0][i] ? redm[1][i] : redm[0][i];
+  }
+}
+
+// count[row] / dmin2[row] = the sum / the minimum over the S segments (thread per row, segments in order)
+__global__ __launch_bounds__(256) void k_manifold_fold(const double* __restrict__ work, int na, int S,
+                                                       int32_t* __restrict__ count, double* __restrict__ dmin2) {
+  const int64_t row = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (row >= na) return;
+  int c = 0;
+  double m = __builtin_huge_val();
+  for (int seg = 0; seg < S; ++seg) {
+    c += (int)work[(int64_t)(2 * seg) * na + row];
+    const double v = work[(int64_t)(2 * seg + 1) * na + row];
+    m = v < m ? v : m;
+  }
+  count[row] = c;
+  dmin2[row] = m;
+}
+
 bool rows_ok(const void* p, int64_t ld, int d) { return p && mg_al16(p) && ld >= d && (ld % 4) == 0; }
 bool dim_ok(int d) { return d >= 4 && d <= 1024 && (d % 4) == 0; }
+bool f64_ok(const void* p) { return p && ((uintptr_t)p & 7) == 0; }
 
 }  // namespace
 
@@ -252,4 +495,40 @@ extern "C" int mg_retrieval_rank(const float* I, int64_t ldi, const float* T, in
   hipLaunchKernelGGL(k_retrieval_rank, dim3(cdiv(n, group)), dim3(256), 0, reinterpret_cast<hipStream_t>(stream), I,
                      ldi, T, ldt, n, d, group, rank, diag);
   return mg_check_launch("mg_retrieval_rank");
+}
+
+extern "C" int mg_knn_radius2(const float* X, int64_t ldx, int n, int d, int k, double* work, int64_t nwork,
+                              double* sq, double* radius2, void* stream) {
+  MG_REQUIRE(dim_ok(d), "d must be a multiple of 4 in [4, 1024]");
+  MG_REQUIRE(n >= 2 && n <= kMaxRows, "n must be in [2, 2^20]");
+  MG_REQUIRE(k >= 1 && k <= kMaxK && k < n, "k must be in [1, 16] and below n");
+  MG_REQUIRE(rows_ok(X, ldx, d), "feature rows must be 16-byte aligned with ld >= d");
+  MG_REQUIRE(f64_ok(work) && f64_ok(sq) && f64_ok(radius2), "bad output pointers");
+  const int tiles = cdiv(n, kTile), S = col_splits(tiles, tiles), tps = cdiv(tiles, S);
+  const int64_t need = (int64_t)n * k * S;
+  MG_REQUIRE(nwork >= need, "work buffer too small: " + std::to_string(need) + " doubles");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(k_row_sq, dim3(cdiv(n, 4)), dim3(256), 0, st, X, ldx, n, d, sq);
+  hipLaunchKernelGGL(k_knn_tiles, dim3(tiles, S), dim3(256), (size_t)4 * k * kTile * sizeof(double), st, X, ldx, n, d, k,
+                     sq, tiles, tps, S, work);
+  hipLaunchKernelGGL(k_knn_fold, dim3(cdiv(n, 256)), dim3(256), 0, st, work, n, k, S, radius2);
+  return mg_check_launch("mg_knn_radius2");
+}
+
+extern "C" int mg_manifold_counts(const float* A, int64_t lda, int na, const double* sqA, const float* B, int64_t ldb,
+                                  int nb, const double* sqB, const double* radius2B, int d, double* work,
+                                  int64_t nwork, int32_t* count, double* dmin2, void* stream) {
+  MG_REQUIRE(dim_ok(d), "d must be a multiple of 4 in [4, 1024]");
+  MG_REQUIRE(na >= 1 && nb >= 1 && na <= kMaxRows && nb <= kMaxRows, "na and nb must be in [1, 2^20]");
+  MG_REQUIRE(rows_ok(A, lda, d) && rows_ok(B, ldb, d), "feature rows must be 16-byte aligned with ld >= d");
+  MG_REQUIRE(f64_ok(sqA) && f64_ok(sqB) && f64_ok(radius2B), "bad squared-norm / radius pointers");
+  MG_REQUIRE(f64_ok(work) && f64_ok(dmin2) && count && ((uintptr_t)count & 3) == 0, "bad output pointers");
+  const int strips = cdiv(na, kTile), tiles = cdiv(nb, kTile), S = col_splits(strips, tiles), tps = cdiv(tiles, S);
+  const int64_t need = (int64_t)2 * na * S;
+  MG_REQUIRE(nwork >= need, "work buffer too small: " + std::to_string(need) + " doubles");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(k_manifold_tiles, dim3(strips, S), dim3(256), 0, st, A, lda, na, sqA, B, ldb, nb, sqB, radius2B, d,
+                     tiles, tps, work);
+  hipLaunchKernelGGL(k_manifold_fold, dim3(cdiv(na, 256)), dim3(256), 0, st, work, na, S, count, dmin2);
+  return mg_check_launch("mg_manifold_counts");
 }

@@ -7,10 +7,12 @@ go through the image tower of ``--clip_weights``; ``kid_clip`` compares the two 
 
   python evaluate_model.py --checkpoint CK --val_images IMAGES.npy --val_embeddings TEXT.npy --clip_weights W
                            [--ema] [--num_samples N] [--truncation_psi P] [--seed S] [--group G] [--batch_size B]
-                           [--num_experts E --topk K --dtype fp32|bf16 --max_resolution R]
+                           [--nearest_k K] [--num_experts E --topk K --dtype fp32|bf16 --max_resolution R]
 
 Prints {"kid_clip": ..., "clip_score": ..., "r_precision": ..., "r_precision_n": ..., "n": ...}; r_precision is NaN
-when fewer than ``--group`` samples were evaluated.  The checkpoint may be any of the shapes generate_images.py takes.
+when fewer than ``--group`` samples were evaluated.  ``--nearest_k K`` adds "precision", "recall", "density",
+"coverage" (improved precision / recall and density / coverage between the two feature sets) and "nearest_k".  The
+checkpoint may be any of the shapes generate_images.py takes.
 """
 import argparse
 import json
@@ -35,6 +37,9 @@ def parse_args(argv=None):
     p.add_argument("--truncation_psi", type=float, default=1.0)
     p.add_argument("--seed", type=int, default=0, help="seed of the latent draws")
     p.add_argument("--group", type=int, default=100, help="R-precision: captions per retrieval group (1 to 128)")
+    p.add_argument("--nearest_k", type=int, default=None,
+                   help="also improved precision / recall and density / coverage with K nearest neighbours "
+                        "(1 to 16, below the number of samples; default: off)")
     p.add_argument("--batch_size", type=int, default=64)
     p.add_argument("--num_experts", type=int, default=4)
     p.add_argument("--topk", type=int, default=None, help="sparse top-k routing (default: dense soft combine)")
@@ -45,6 +50,8 @@ def parse_args(argv=None):
         p.error("--group must be between 1 and 128")
     if args.num_samples is not None and args.num_samples < 2:
         p.error("--num_samples must be at least 2")
+    if args.nearest_k is not None and not 1 <= args.nearest_k <= 16:
+        p.error("--nearest_k must be between 1 and 16")
     return args
 
 
@@ -63,7 +70,7 @@ def main(argv=None):
     loader = DataLoader(ProcessedMSCOCODataset(args.val_images, args.val_embeddings), batch_size=args.batch_size,
                         shuffle=False)
     m = M.evaluate_aurora_gan(generator, loader, num_samples=args.num_samples, truncation_psi=args.truncation_psi,
-                              seed=args.seed, group=args.group)
+                              seed=args.seed, group=args.group, nearest_k=args.nearest_k)
     print(json.dumps(m))
     return m
 

@@ -1,8 +1,9 @@
 """Quality metrics of a generator over CLIP image features (no reference counterpart: the reference measures
 validation losses only, t2i_moe_gan.py:1519-1639).
 
-Three numbers, all from the image tower in the tree (clip_vit.ClipImageEncoder.encode_generated on real and generated
-images alike, so both sides see the same clamp / resize / patchify) and the captions' pooled text embeddings:
+Three numbers by default, all from the image tower in the tree (clip_vit.ClipImageEncoder.encode_generated on real
+and generated images alike, so both sides see the same clamp / resize / patchify) and the captions' pooled text
+embeddings:
 
   kid_clip     the unbiased MMD^2 estimate with the cubic kernel k(a, b) = (<a, b> / d + 1)^3 between the generated
                and the real images' raw tower features, over the whole sets (KID's kernel; not subset-averaged):
@@ -11,6 +12,16 @@ images alike, so both sides see the same clamp / resize / patchify) and the capt
   r_precision  the share of generated images whose own caption is the best match among the ``group`` captions of
                its group of consecutive rows (ops.retrieval_rank, rank == 0); rows of an incomplete last group are
                left out, so chance level stays 1 / group.
+
+With ``nearest_k`` set, four more over the same raw tower features, F the n generated rows and R the m real rows
+(prdc; improved precision / recall, Kynkäänniemi et al. 2019, and density / coverage, Naeem et al. 2020).  With
+D(a, b) the squared distance, radius2_S[i] the k-th smallest D(s_i, s_j) over j != i (ops.knn_radius2) and
+count_{A->B}[a] = #{b : D(a, b) <= radius2_B[b]}, dmin2_{A->B}[a] = min_b D(a, b) (ops.manifold_counts):
+
+  precision    the share of f with count_{F->R}[f] > 0       (fidelity: f lies in some real row's k-NN ball)
+  density      sum_f count_{F->R}[f] / (k n)                 (the same, counting the balls; may exceed 1)
+  recall       the share of r with count_{R->F}[r] > 0       (diversity: r lies in some generated row's ball)
+  coverage     the share of r with dmin2_{R->F}[r] <= radius2_R[r]   (r's own ball holds a generated row)
 
 Fréchet distance over Inception features is out of reach offline (no Inception weights); these are the same family of
 metrics over the tower this build ships.
@@ -33,6 +44,42 @@ def kid_from_sums(sums, n, m):
     return sxx / (n * (n - 1)) + syy / (m * (m - 1)) - 2.0 * sxy / (n * m)
 
 
+def prdc_from_counts(count_fr, count_rf, dmin2_rf, radius2_r, nearest_k):
+    """{'precision', 'recall', 'density', 'coverage', 'nearest_k'} from the arrays of ops.manifold_counts (tensors,
+    arrays or lists): count_fr [n] of the generated rows against the real ones, count_rf [m] and dmin2_rf [m] of the
+    real rows against the generated ones, and the real rows' radius2_r [m].  Host arithmetic in Python floats."""
+    as_list = lambda a: a.tolist() if hasattr(a, "tolist") else list(a)  # noqa: E731
+    cfr, crf, dmin, rad = as_list(count_fr), as_list(count_rf), as_list(dmin2_rf), as_list(radius2_r)
+    n, m, k = len(cfr), len(crf), int(nearest_k)
+    if n < 1 or m < 1 or len(dmin) != m or len(rad) != m or k < 1:
+        raise ValueError(f"prdc_from_counts: {n} generated and {m} real counts, {len(dmin)} minima, {len(rad)} radii, "
+                         f"nearest_k {k}")
+    return {"precision": sum(1 for c in cfr if c > 0) / n,
+            "recall": sum(1 for c in crf if c > 0) / m,
+            "density": sum(int(c) for c in cfr) / (k * n),
+            "coverage": sum(1 for dm, r in zip(dmin, rad) if dm <= r) / m,
+            "nearest_k": k}
+
+
+def prdc(fake, real, nearest_k=5, real_knn=None):
+    """Improved precision / recall and density / coverage of fp32 device rows ``fake`` [n, d] against ``real``
+    [m, d] (the module docstring has the definitions): two ops.knn_radius2 calls and two ops.manifold_counts calls,
+    then prdc_from_counts.  ``nearest_k`` must be below min(n, m).  ``real_knn``: the (sq, radius2) of ``real`` from
+    an earlier ops.knn_radius2 with the same ``nearest_k``, to save that call.  The features pass through as they
+    are: non-finite features are the caller's responsibility (a NaN distance is in no ball and is no minimum)."""
+    n, m, k = int(fake.shape[0]), int(real.shape[0]), int(nearest_k)
+    if fake.dim() != 2 or real.dim() != 2 or fake.shape[1] != real.shape[1]:
+        raise ValueError(f"prdc: fake {tuple(fake.shape)}, real {tuple(real.shape)}")
+    if not 1 <= k < min(n, m):
+        raise ValueError(f"prdc: nearest_k must be in [1, min(n, m)) = [1, {min(n, m)}), got {k}")
+    fake, real = fake.float(), real.float()
+    sq_f, rad_f = ops.knn_radius2(fake, k)
+    sq_r, rad_r = ops.knn_radius2(real, k) if real_knn is None else real_knn
+    count_fr, _ = ops.manifold_counts(fake, sq_f, real, sq_r, rad_r)
+    count_rf, dmin2_rf = ops.manifold_counts(real, sq_r, fake, sq_f, rad_f)
+    return prdc_from_counts(count_fr, count_rf, dmin2_rf, rad_r, k)
+
+
 def _unit_rows(x):
     """Rows scaled to unit length in fp64, rounded once to fp32 (each entry within 2^-24 relative of the exact one);
     a zero row stays zero."""
@@ -40,9 +87,10 @@ def _unit_rows(x):
     return (x64 / x64.norm(dim=1, keepdim=True).clamp_min(1e-300)).float().contiguous()
 
 
-def clip_metrics(fake_feat, real_feat, text_feat, group=100):
+def clip_metrics(fake_feat, real_feat, text_feat, group=100, nearest_k=None, real_knn=None):
     """{'kid_clip', 'clip_score', 'r_precision', 'r_precision_n'} from fp32 device rows: generated-image features
-    [n, d], real-image features [m, d], and the text features [n, d] the n images were generated from."""
+    [n, d], real-image features [m, d], and the text features [n, d] the n images were generated from.  With
+    ``nearest_k`` also the five keys of prdc(fake, real, nearest_k, real_knn)."""
     fake, real, text = fake_feat.float(), real_feat.float(), text_feat.float()
     n, d = fake.shape
     m = real.shape[0]
@@ -53,10 +101,13 @@ def clip_metrics(fake_feat, real_feat, text_feat, group=100):
     rank, diag = ops.retrieval_rank(_unit_rows(fake), _unit_rows(text), group)
     complete = (n // group) * group
     hits = int((rank[:complete] == 0).sum()) if complete else 0
-    return {"kid_clip": kid_from_sums(sums.tolist(), n, m),
-            "clip_score": 100.0 * float(torch.nan_to_num(diag).double().clamp_min(0.0).mean()),
-            "r_precision": hits / complete if complete else float("nan"),
-            "r_precision_n": complete}
+    out = {"kid_clip": kid_from_sums(sums.tolist(), n, m),
+           "clip_score": 100.0 * float(torch.nan_to_num(diag).double().clamp_min(0.0).mean()),
+           "r_precision": hits / complete if complete else float("nan"),
+           "r_precision_n": complete}
+    if nearest_k is not None:
+        out.update(prdc(fake, real, nearest_k, real_knn))
+    return out
 
 
 def gather_rows(t, process_group=None):
@@ -87,14 +138,17 @@ def _nhwc(images):
 
 
 def evaluate_generator(generator, loader, tower, num_samples=None, truncation_psi=1.0, seed=0, use_ema=False,
-                       group=100, process_group=None, return_features=False):
+                       group=100, process_group=None, return_features=False, nearest_k=None):
     """clip_metrics of ``generator`` on the (image, text[, token rows ...]) batches of ``loader``, plus 'n' (images
     generated).  Eval-mode forward (mean router weights, hard top-1) with latents from a generator seeded with
     ``seed``, so successive evaluations of one loader see the same z; ``use_ema`` evaluates the moving average
     (``generator.ema_generator()``).  ``num_samples`` caps the samples taken (split over the ranks of
     ``process_group``; each rank encodes its shard, the feature rows are gathered in rank order and every rank
     computes the same numbers).  The real images' features are cached on the loader object for the next call with
-    the same tower and cap.  Modes are restored.  ``return_features``: also {'fake', 'real', 'text'}."""
+    the same tower and cap.  Modes are restored.  ``return_features``: also {'fake', 'real', 'text'}.
+    ``nearest_k`` (None: off, the dict as it was) adds precision / recall / density / coverage (prdc) and
+    'nearest_k'; the real set's squared norms and radii stay in the loader's cache with the ``nearest_k`` they were
+    computed for, since they are the same for every evaluation of a run."""
     rank, world = 0, 1
     if process_group is not None:
         import torch.distributed as dist
@@ -142,17 +196,33 @@ def evaluate_generator(generator, loader, tower, num_samples=None, truncation_ps
     feats = {"fake": torch.cat(fake), "real": cache["real"] if cache is not None else torch.cat(real),
              "text": torch.cat(text_rows)}
     if cache is None:
+        cache = {"tower": tower, "cap": cap, "real": feats["real"]}
         try:
-            loader._moegan_eval_cache = {"tower": tower, "cap": cap, "real": feats["real"]}
+            loader._moegan_eval_cache = cache
         except AttributeError:
             pass  # a loader object that takes no attributes: nothing is cached
     feats = {k: gather_rows(v.contiguous(), process_group) for k, v in feats.items()}
-    metrics = clip_metrics(feats["fake"], feats["real"], feats["text"], group)
+    real_knn = None
+    if nearest_k is not None:
+        nearest_k = int(nearest_k)
+        rows = min(feats["fake"].shape[0], feats["real"].shape[0])
+        if not 1 <= nearest_k < rows:
+            raise ValueError(f"evaluate_generator: nearest_k must be in [1, {rows}) for these sets, got {nearest_k}")
+        knn = cache.get("knn")  # of the gathered real rows, which the tower and the cap fix
+        if knn is None or knn["nearest_k"] != nearest_k:
+            sq, radius2 = ops.knn_radius2(feats["real"], nearest_k)
+            knn = cache["knn"] = {"nearest_k": nearest_k, "sq": sq, "radius2": radius2}
+        real_knn = (knn["sq"], knn["radius2"])
+    metrics = clip_metrics(feats["fake"], feats["real"], feats["text"], group, nearest_k, real_knn)
     metrics["n"] = int(feats["fake"].shape[0])
     return (metrics, feats) if return_features else metrics
 
 
 def format_metrics(m):
     r = "n/a" if math.isnan(m["r_precision"]) else f"{m['r_precision']:.4f}"
-    return (f"KID_clip: {m['kid_clip']:.6f}, CLIP_score: {m['clip_score']:.3f}, "
+    text = (f"KID_clip: {m['kid_clip']:.6f}, CLIP_score: {m['clip_score']:.3f}, "
             f"R_precision: {r} (of {m['r_precision_n']}), images: {m['n']}")
+    if "precision" in m:
+        text += (f", Precision/Recall/Density/Coverage (k={m['nearest_k']}): {m['precision']:.4f}/{m['recall']:.4f}/"
+                 f"{m['density']:.4f}/{m['coverage']:.4f}")
+    return text

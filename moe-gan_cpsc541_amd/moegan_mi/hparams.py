@@ -14,7 +14,8 @@ SURVEY.md §5) as the 16x16 / 8x8 CLIP weights.
 import json
 
 # sagemaker_train.py:94-99
-INT_KEYS = ("batch_size", "epochs", "kl_annealing_epochs", "lr_warmup_epochs", "eval_every", "eval_samples")
+INT_KEYS = ("batch_size", "epochs", "kl_annealing_epochs", "lr_warmup_epochs", "eval_every", "eval_samples",
+            "eval_nearest_k")
 FLOAT_KEYS = ("learning_rate", "beta1", "beta2", "r1_gamma", "clip_weight_16", "clip_weight_8", "kl_weight",
               "balance_weight", "ema_kimg", "ema_rampup")
 # keys of the HPO config that name CLIP weights the training entry point knows under other names
@@ -40,6 +41,8 @@ TRAIN_KWARGS = {
     # unless set), over at most eval_samples samples
     "eval_every": ("eval_every", None),
     "eval_samples": ("eval_samples", None),
+    # ... and, with eval_nearest_k set, precision / recall / density / coverage with that many nearest neighbours
+    "eval_nearest_k": ("eval_nearest_k", None),
 }
 # fixed by the SageMaker entry point (sagemaker_train.py:287-292)
 TRAIN_FIXED = {"log_interval": 100, "save_interval": 500, "gradient_accumulation_steps": 8,

@@ -1304,3 +1304,49 @@ def retrieval_rank(I, T, group):
     diag = torch.empty(n, device=I.device, dtype=torch.float32)
     call("mg_retrieval_rank", ptr(I), I.stride(0), ptr(T), T.stride(0), n, d, int(group), ptr(rank), ptr(diag), S())
     return rank, diag
+
+
+def prdc_splits(rows, cols):
+    """Column segments of mg_knn_radius2 / mg_manifold_counts for ``rows`` rows against ``cols`` columns
+    (include/moegan_hip.h, S(rows, cols)): sizes the caller-owned work buffers."""
+    strips, tiles = -(-rows // MMD_TILE), -(-cols // MMD_TILE)
+    return max(1, min(tiles, 8, -(-512 // max(strips, 1))))
+
+
+def knn_radius2(X, k, work=None):
+    """(sq float64 [n], radius2 float64 [n]) of fp32 rows X [n, d] (mg_knn_radius2): sq[i] = |x_i|^2 summed in fp64,
+    radius2[i] = the k-th smallest squared distance from row i to the other rows (self left out by index), with
+    D(a, b) = (sq_a + sq_b) - 2 <a, b> in fp64 over the exact-fp32 MFMA dot.  Bitwise repeatable."""
+    X = _feature_rows(X, "X")
+    n, d = X.shape
+    k = int(k)
+    need = max(n, 1) * max(k, 1) * prdc_splits(n, n)
+    if work is None:
+        work = torch.empty(need, device=X.device, dtype=torch.float64)
+    sq = torch.empty(n, device=X.device, dtype=torch.float64)
+    radius2 = torch.empty(n, device=X.device, dtype=torch.float64)
+    call("mg_knn_radius2", ptr(X), X.stride(0), n, d, k, ptr(work), work.numel(), ptr(sq), ptr(radius2), S())
+    return sq, radius2
+
+
+def manifold_counts(A, sqA, B, sqB, radius2B, work=None):
+    """(count int32 [na], dmin2 float64 [na]) of rows A [na, d] against rows B [nb, d] (mg_manifold_counts), given
+    both sets' squared norms and B's radii from knn_radius2: count[a] = the number of b with D(a, b) <= radius2B[b],
+    dmin2[a] = min_b D(a, b)."""
+    A, B = _feature_rows(A, "A"), _feature_rows(B, "B")
+    na, d = A.shape
+    nb = B.shape[0]
+    if B.shape[1] != d:
+        raise L.MGError(f"manifold_counts: A has {d} columns, B {B.shape[1]}")
+    for t, rows, what in ((sqA, na, "sqA"), (sqB, nb, "sqB"), (radius2B, nb, "radius2B")):
+        if t.dtype != torch.float64 or tuple(t.shape) != (rows,) or not t.is_cuda or not t.is_contiguous():
+            raise L.MGError(f"manifold_counts: {what} must be a contiguous float64 device vector of {rows}, got "
+                            f"{tuple(t.shape)} {t.dtype} {t.device}")
+    need = 2 * max(na, 1) * prdc_splits(na, nb)
+    if work is None:
+        work = torch.empty(need, device=A.device, dtype=torch.float64)
+    count = torch.empty(na, device=A.device, dtype=torch.int32)
+    dmin2 = torch.empty(na, device=A.device, dtype=torch.float64)
+    call("mg_manifold_counts", ptr(A), A.stride(0), na, ptr(sqA), ptr(B), B.stride(0), nb, ptr(sqB), ptr(radius2B), d,
+         ptr(work), work.numel(), ptr(count), ptr(dmin2), S())
+    return count, dmin2

@@ -112,11 +112,18 @@ def parse_args(argv=None):
                    help="with --eval_every: evaluate at most M validation samples (default: all)")
     p.add_argument("--eval_truncation_psi", type=float, default=1.0,
                    help="with --eval_every: truncation psi of the evaluated samples")
+    p.add_argument("--eval_nearest_k", type=int, default=None,
+                   help="with --eval_every: also improved precision / recall and density / coverage with K nearest "
+                        "neighbours (val_precision / val_recall / val_density / val_coverage; default: off)")
     args = p.parse_args(argv)
     if args.clip_grad and not args.clip_weights:
         p.error("--clip_grad needs --clip_weights (the CLIP image tower whose backward it runs)")
     if args.eval_every and not args.clip_weights:
         p.error("--eval_every needs --clip_weights (the CLIP image tower whose features it compares)")
+    if args.eval_nearest_k is not None and not args.eval_every:
+        p.error("--eval_nearest_k needs --eval_every (the evaluation it adds to)")
+    if args.eval_nearest_k is not None and args.eval_nearest_k < 1:
+        p.error("--eval_nearest_k must be at least 1")
     return args
 
 
@@ -198,6 +205,8 @@ def main(argv=None):
     if args.eval_every:
         kw.setdefault("eval_every", args.eval_every)
         kw.setdefault("eval_samples", args.eval_samples)
+        if args.eval_nearest_k is not None:
+            kw.setdefault("eval_nearest_k", args.eval_nearest_k)
     if kw.get("eval_every"):
         kw.setdefault("eval_truncation_psi", args.eval_truncation_psi)
     G, D = M.train_aurora_gan(train_dl, val_dataloader=val_dl, device=device, save_dir=args.save_dir,
