@@ -763,6 +763,22 @@ int mg_manifold_counts(const float* A, int64_t lda, int na, const double* sqA, c
                        const double* sqB, const double* radius2B, int d, double* work, int64_t nwork, int32_t* count,
                        double* dmin2, void* stream);
 
+/* Raw first and second moments about zero of the rows of X [n, d], 1 <= n, in fp64 (the statistics of a Fréchet
+   distance: mean = s1 / n, covariance = (s2 - s1 s1^T / n) / (n - 1)):
+     s1[j] = sum_i x_ij        s2[j][k] = sum_i x_ij x_ik        (s2 is [d, d] with row pitch d)
+   Each fp32 entry is widened to fp64, so every product is exact and the fp64 additions are the only roundings:
+   |s2[j][k] - exact| <= (n + 2) 2^-53 (sum_i |x_ij x_ik| + |old s2[j][k]|), and s1 alike with |x_ij|.  The matrix
+   runs on v_mfma_f64_16x16x4_f64 with the rows of X as the reduction dimension: 64 x 64 column tiles with ci <= cj,
+   the rows cut into S segments of ceil(ceil(n / S) / 4) * 4 rows,
+     S(n, d) = max(1, min(ceil(n / 256), 16, ceil(1024 / T))),  T = t (t + 1) / 2,  t = ceil(d / 64).
+   Every block stores its tile's partial (the diagonal tiles' blocks also their 64 column sums) into `work`, and a
+   second launch folds the segments in order and writes both triangles of s2 from the one sum, so s2 is bitwise
+   symmetric: no atomics, bitwise repeatable.  With accumulate == 0 the outputs are overwritten; with accumulate != 0
+   the folded sums are added to what s1 / s2 hold (one more fp64 addition per entry; s2's upper triangle is what is
+   read).  `work` is caller-owned device memory of nwork >= S(n, d) (d d + d) doubles; no other memory is used. */
+int mg_feature_moments(const float* X, int64_t ldx, int n, int d, double* work, int64_t nwork, double* s1, double* s2,
+                       int accumulate, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

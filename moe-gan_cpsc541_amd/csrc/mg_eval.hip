@@ -462,6 +462,146 @@ __global__ __launch_bounds__(256) void k_manifold_fold(const double* __restrict_
   dmin2[row] = m;
 }
 
+// ---- raw first and second moments of feature rows (the statistics of a Fréchet distance) ----
+// s2 = X^T X is a product over the ROWS of X, so the reduction dimension is what the kernels above tile: a block
+// owns one 64 x 64 tile (ci <= cj) of the d x d result and one of S row segments, stages kMR rows of the two column
+// blocks at a time with the same Stage (as two 32-column halves each), and feeds v_mfma_f64_16x16x4_f64 with the
+// entries widened to fp64 (a product of two fp32 values is exact in fp64; the additions are the only roundings).
+// Operand maps of the f64 MFMA: lane l gives A[m = l & 15][k = l >> 4] and B[k = l >> 4][n = l & 15], one fp64 each;
+// D[m][n] sits at lane (n = l & 15), register reg with m = (l >> 4) + 4 reg -- NOT the f32 forms' row map.  Here k is
+// a staged row and m / n are columns of X, so both operands are "row l >> 4 of the k step, column l & 15 of a
+// 16-column strip".  Nothing depends on the order in which the instruction adds its four k.
+
+typedef double f64x4_t __attribute__((ext_vector_type(4)));
+constexpr int kMR = 32;             // rows per staged chunk of mg_feature_moments
+constexpr int kMomMaxSeg = 16;      // row segments per launch <= 16
+constexpr int kMomBlocks = 1024;    // ... and no more than bring the grid to about this many blocks
+constexpr int kMomSegRows = 256;    // ... and none for fewer rows than this per segment
+
+// row segments of mg_feature_moments (the header documents it: the caller sizes `work` by it)
+int moment_segments(int n, int d) {
+  const int t = cdiv(d, kTile), T = t * (t + 1) / 2;
+  return std::max(1, std::min({cdiv(n, kMomSegRows), kMomMaxSeg, cdiv(kMomBlocks, T)}));
+}
+
+// Block (t, seg): tile t = cj (cj + 1) / 2 + ci (ci <= cj) of X^T X over the rows [seg rps, (seg + 1) rps) below n.
+// Wave (wr, wc) holds the 32 x 32 quadrant as 2 x 2 MFMA tiles.  The partial goes to the segment's slab of `work`
+// ([d][d] then [d]); a diagonal tile's block also sums its 64 columns over the staged rows (thread (c = t & 63,
+// q = t >> 6) takes rows 8 q .. 8 q + 7 of every chunk, then q = 0 .. 3 in order) for s1.
+__global__ __launch_bounds__(256) void k_moment_tiles(const float* __restrict__ X, int64_t ldx, int n, int d, int rps,
+                                                      double* __restrict__ work) {
+  __shared__ float As[2][kMR][kLDP], Bs[2][kMR][kLDP];
+  __shared__ double red[4][kTile];
+  const int t = blockIdx.x, seg = blockIdx.y;
+  int cj = (int)((sqrtf(8.f * (float)t + 1.f) - 1.f) * 0.5f);
+  while (cj * (cj + 1) / 2 > t) --cj;
+  while ((cj + 1) * (cj + 2) / 2 <= t) ++cj;
+  const int ci = t - cj * (cj + 1) / 2;
+  const bool diag = ci == cj;  // (block-uniform)
+  const int ca = ci * kTile, cb = cj * kTile;
+  const int64_t row0 = (int64_t)seg * rps, row1 = std::min<int64_t>(n, row0 + rps);
+  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, lc = lane & 15, lk = lane >> 4;
+  const int wr = w >> 1, wc = w & 1;
+  const float(*Ah)[kLDP] = As[wr];
+  const float(*Bh)[kLDP] = diag ? As[wc] : Bs[wc];
+
+  f64x4_t acc[2][2];
+#pragma unroll
+  for (int a = 0; a < 2; ++a)
+#pragma unroll
+    for (int b = 0; b < 2; ++b)
+#pragma unroll
+      for (int i = 0; i < 4; ++i) acc[a][b][i] = 0.0;
+  double colsum = 0.0;
+  const int sc = threadIdx.x & 63, sq = threadIdx.x >> 6;
+
+  Stage<kMR> a0, a1, b0, b1;
+  a0.load(X, ldx, row0, row1, ca, d);
+  a1.load(X, ldx, row0, row1, ca + kKC, d);
+  if (!diag) {
+    b0.load(X, ldx, row0, row1, cb, d);
+    b1.load(X, ldx, row0, row1, cb + kKC, d);
+  }
+  for (int64_t r = row0; r < row1; r += kMR) {
+    a0.store(As[0]);
+    a1.store(As[1]);
+    if (!diag) {
+      b0.store(Bs[0]);
+      b1.store(Bs[1]);
+    }
+    __syncthreads();
+    if (r + kMR < row1) {  // the next chunk's loads fly under this chunk's MFMAs
+      a0.load(X, ldx, r + kMR, row1, ca, d);
+      a1.load(X, ldx, r + kMR, row1, ca + kKC, d);
+      if (!diag) {
+        b0.load(X, ldx, r + kMR, row1, cb, d);
+        b1.load(X, ldx, r + kMR, row1, cb + kKC, d);
+      }
+    }
+    if (diag) {
+#pragma unroll
+      for (int i = 0; i < kMR / 4; ++i) colsum += (double)As[sc >> 5][sq * (kMR / 4) + i][sc & 31];
+    }
+#pragma unroll
+    for (int ks = 0; ks < kMR / 4; ++ks) {
+      const int kr = 4 * ks + lk;
+      double a[2], b[2];
+#pragma unroll
+      for (int s = 0; s < 2; ++s) {
+        a[s] = (double)Ah[kr][16 * s + lc];
+        b[s] = (double)Bh[kr][16 * s + lc];
+      }
+#pragma unroll
+      for (int sa = 0; sa < 2; ++sa)
+#pragma unroll
+        for (int sb = 0; sb < 2; ++sb)
+          acc[sa][sb] = __builtin_amdgcn_mfma_f64_16x16x4f64(a[sa], b[sb], acc[sa][sb], 0, 0, 0);
+    }
+    __syncthreads();
+  }
+
+  double* slab = work + (int64_t)seg * ((int64_t)d * d + d);
+#pragma unroll
+  for (int sa = 0; sa < 2; ++sa)
+#pragma unroll
+    for (int sb = 0; sb < 2; ++sb) {
+      const int k = cb + wc * 32 + sb * 16 + lc;
+#pragma unroll
+      for (int reg = 0; reg < 4; ++reg) {
+        const int j = ca + wr * 32 + sa * 16 + lk + 4 * reg;
+        if (j < d && k < d) slab[(int64_t)j * d + k] = acc[sa][sb][reg];
+      }
+    }
+  if (diag) {
+    red[sq][sc] = colsum;
+    __syncthreads();
+    if (threadIdx.x < kTile && ca + (int)threadIdx.x < d)
+      slab[(int64_t)d * d + ca + threadIdx.x] =
+          ((red[0][threadIdx.x] + red[1][threadIdx.x]) + red[2][threadIdx.x]) + red[3][threadIdx.x];
+  }
+}
+
+// Thread per entry of the upper triangle of s2 (j <= k) and per entry of s1: the S segments' partials in order, then
+// what the output held when `accumulate`; s2[j][k] and s2[k][j] are stored from the one sum.
+__global__ __launch_bounds__(256) void k_moment_fold(const double* __restrict__ work, int d, int S, int accumulate,
+                                                     double* __restrict__ s1, double* __restrict__ s2) {
+  const int64_t dd = (int64_t)d * d, slab = dd + d;
+  const int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= slab) return;
+  const int j = (int)(idx / d), k = (int)(idx - (int64_t)j * d);
+  if (idx < dd && j > k) return;
+  double s = work[idx];
+  for (int seg = 1; seg < S; ++seg) s += work[seg * slab + idx];
+  if (idx < dd) {
+    if (accumulate) s = s2[idx] + s;
+    s2[idx] = s;
+    s2[(int64_t)k * d + j] = s;
+  } else {
+    if (accumulate) s = s1[idx - dd] + s;
+    s1[idx - dd] = s;
+  }
+}
+
 bool rows_ok(const void* p, int64_t ld, int d) { return p && mg_al16(p) && ld >= d && (ld % 4) == 0; }
 bool dim_ok(int d) { return d >= 4 && d <= 1024 && (d % 4) == 0; }
 bool f64_ok(const void* p) { return p && ((uintptr_t)p & 7) == 0; }
@@ -531,4 +671,21 @@ extern "C" int mg_manifold_counts(const float* A, int64_t lda, int na, const dou
                      tiles, tps, work);
   hipLaunchKernelGGL(k_manifold_fold, dim3(cdiv(na, 256)), dim3(256), 0, st, work, na, S, count, dmin2);
   return mg_check_launch("mg_manifold_counts");
+}
+
+extern "C" int mg_feature_moments(const float* X, int64_t ldx, int n, int d, double* work, int64_t nwork, double* s1,
+                                  double* s2, int accumulate, void* stream) {
+  MG_REQUIRE(dim_ok(d), "d must be a multiple of 4 in [4, 1024]");
+  MG_REQUIRE(n >= 1 && n <= kMaxRows, "n must be in [1, 2^20]");
+  MG_REQUIRE(rows_ok(X, ldx, d), "feature rows must be 16-byte aligned with ld >= d");
+  MG_REQUIRE(f64_ok(work) && f64_ok(s1) && f64_ok(s2), "bad output pointers");
+  const int t = cdiv(d, kTile), S = moment_segments(n, d);
+  const int rps = cdiv(cdiv(n, S), 4) * 4;  // segment boundaries on multiples of the MFMA's k
+  const int64_t slab = (int64_t)d * d + d, need = slab * S;
+  MG_REQUIRE(nwork >= need, "work buffer too small: " + std::to_string(need) + " doubles");
+  hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+  hipLaunchKernelGGL(k_moment_tiles, dim3(t * (t + 1) / 2, S), dim3(256), 0, st, X, ldx, n, d, rps, work);
+  hipLaunchKernelGGL(k_moment_fold, dim3((unsigned)cdiv(slab, (int64_t)256)), dim3(256), 0, st, work, d, S,
+                     accumulate ? 1 : 0, s1, s2);
+  return mg_check_launch("mg_feature_moments");
 }

@@ -7,12 +7,16 @@ go through the image tower of ``--clip_weights``; ``kid_clip`` compares the two 
 
   python evaluate_model.py --checkpoint CK --val_images IMAGES.npy --val_embeddings TEXT.npy --clip_weights W
                            [--ema] [--num_samples N] [--truncation_psi P] [--seed S] [--group G] [--batch_size B]
-                           [--nearest_k K] [--num_experts E --topk K --dtype fp32|bf16 --max_resolution R]
+                           [--nearest_k K] [--frechet] [--reference_stats FILE] [--save_stats FILE]
+                           [--num_experts E --topk K --dtype fp32|bf16 --max_resolution R]
 
 Prints {"kid_clip": ..., "clip_score": ..., "r_precision": ..., "r_precision_n": ..., "n": ...}; r_precision is NaN
 when fewer than ``--group`` samples were evaluated.  ``--nearest_k K`` adds "precision", "recall", "density",
-"coverage" (improved precision / recall and density / coverage between the two feature sets) and "nearest_k".  The
-checkpoint may be any of the shapes generate_images.py takes.
+"coverage" (improved precision / recall and density / coverage between the two feature sets) and "nearest_k".
+``--frechet`` adds "fd_clip", the Fréchet distance between the generated and the validation images' features;
+``--reference_stats FILE`` measures it against the mean and covariance of an .npz with 'mu' and 'sigma' (the
+reference's reference_stats.npz layout, made with the same tower) instead, and ``--save_stats FILE`` writes the
+validation images' 'mu' / 'sigma' / 'n' in that layout; both imply ``--frechet``.  The checkpoint may be any of the shapes generate_images.py takes.
 """
 import argparse
 import json
@@ -40,6 +44,12 @@ def parse_args(argv=None):
     p.add_argument("--nearest_k", type=int, default=None,
                    help="also improved precision / recall and density / coverage with K nearest neighbours "
                         "(1 to 16, below the number of samples; default: off)")
+    p.add_argument("--frechet", action="store_true",
+                   help="also the Fréchet distance between the generated and the validation images' features")
+    p.add_argument("--reference_stats", type=str, default=None,
+                   help="measure the Fréchet distance against this .npz of 'mu' and 'sigma' instead (implies --frechet)")
+    p.add_argument("--save_stats", type=str, default=None,
+                   help="write the validation images' 'mu' / 'sigma' / 'n' to this .npz (implies --frechet)")
     p.add_argument("--batch_size", type=int, default=64)
     p.add_argument("--num_experts", type=int, default=4)
     p.add_argument("--topk", type=int, default=None, help="sparse top-k routing (default: dense soft combine)")
@@ -52,6 +62,8 @@ def parse_args(argv=None):
         p.error("--num_samples must be at least 2")
     if args.nearest_k is not None and not 1 <= args.nearest_k <= 16:
         p.error("--nearest_k must be between 1 and 16")
+    if args.reference_stats or args.save_stats:
+        args.frechet = True
     return args
 
 
@@ -69,8 +81,15 @@ def main(argv=None):
     M.load_clip_weights(args.clip_weights, device)
     loader = DataLoader(ProcessedMSCOCODataset(args.val_images, args.val_embeddings), batch_size=args.batch_size,
                         shuffle=False)
+    kw = {}
+    if args.frechet:
+        kw = dict(frechet=True, reference_stats=args.reference_stats, return_features=bool(args.save_stats))
     m = M.evaluate_aurora_gan(generator, loader, num_samples=args.num_samples, truncation_psi=args.truncation_psi,
-                              seed=args.seed, group=args.group, nearest_k=args.nearest_k)
+                              seed=args.seed, group=args.group, nearest_k=args.nearest_k, **kw)
+    if args.save_stats:
+        from moegan_mi.evaluate import FeatureMoments
+        m, feats = m
+        FeatureMoments(feats["real"].shape[1], feats["real"].device).update(feats["real"]).save(args.save_stats)
     print(json.dumps(m))
     return m
 

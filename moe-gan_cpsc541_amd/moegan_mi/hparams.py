@@ -18,6 +18,8 @@ INT_KEYS = ("batch_size", "epochs", "kl_annealing_epochs", "lr_warmup_epochs", "
             "eval_nearest_k")
 FLOAT_KEYS = ("learning_rate", "beta1", "beta2", "r1_gamma", "clip_weight_16", "clip_weight_8", "kl_weight",
               "balance_weight", "ema_kimg", "ema_rampup")
+# this build's switches: "true" / "1" / "yes" / "on" (any case) turn one on, "false" / "0" / "no" / "off" / "" off
+BOOL_KEYS = ("eval_frechet",)
 # keys of the HPO config that name CLIP weights the training entry point knows under other names
 CLIP_ALIASES = {"clip_weight_64": "clip_weight_16", "clip_weight_32": "clip_weight_8"}
 
@@ -43,12 +45,25 @@ TRAIN_KWARGS = {
     "eval_samples": ("eval_samples", None),
     # ... and, with eval_nearest_k set, precision / recall / density / coverage with that many nearest neighbours
     "eval_nearest_k": ("eval_nearest_k", None),
+    # ... and, with eval_frechet on, the Fréchet distance over the same features
+    "eval_frechet": ("eval_frechet", False),
 }
 # fixed by the SageMaker entry point (sagemaker_train.py:287-292)
 TRAIN_FIXED = {"log_interval": 100, "save_interval": 500, "gradient_accumulation_steps": 8,
                "checkpoint_activation": True, "batch_memory_limit": 20.0, "max_resolution": 16}
 
 SCALING_TYPES = ("Auto", "Linear", "Logarithmic", "ReverseLogarithmic")
+
+
+def _coerce_bool(key, value):
+    if isinstance(value, str):
+        v = value.strip().lower()
+        if v in ("true", "1", "yes", "on"):
+            return True
+        if v in ("false", "0", "no", "off", ""):
+            return False
+        raise ValueError(f"{key}: expected a boolean, got {value!r}")
+    return bool(value)
 
 
 def coerce_hyperparameters(raw):
@@ -60,6 +75,8 @@ def coerce_hyperparameters(raw):
             params[key] = int(value)
         elif key in FLOAT_KEYS or key in CLIP_ALIASES:
             params[key] = float(value)
+        elif key in BOOL_KEYS:
+            params[key] = _coerce_bool(key, value)
         else:
             params[key] = value
     return params

@@ -1350,3 +1350,32 @@ def manifold_counts(A, sqA, B, sqB, radius2B, work=None):
     call("mg_manifold_counts", ptr(A), A.stride(0), na, ptr(sqA), ptr(B), B.stride(0), nb, ptr(sqB), ptr(radius2B), d,
          ptr(work), work.numel(), ptr(count), ptr(dmin2), S())
     return count, dmin2
+
+
+def moment_segments(n, d):
+    """Row segments of mg_feature_moments for ``n`` rows of width ``d`` (include/moegan_hip.h, S(n, d)): sizes the
+    caller-owned work buffer, moment_segments(n, d) * (d * d + d) doubles."""
+    t = -(-d // MMD_TILE)
+    return max(1, min(-(-n // 256), 16, -(-1024 // max(t * (t + 1) // 2, 1))))
+
+
+def feature_moments(X, s1=None, s2=None, accumulate=False, work=None):
+    """(s1 float64 [d], s2 float64 [d, d]) of fp32 rows X [n, d] (mg_feature_moments): s1[j] = sum_i x_ij and
+    s2[j][k] = sum_i x_ij x_ik, exact fp64 products on the fp64 MFMA, fixed-order fp64 sums; s2 is bitwise symmetric
+    and the call bitwise repeatable.  ``accumulate`` adds to the given ``s1`` / ``s2`` instead of overwriting them."""
+    X = _feature_rows(X, "X")
+    n, d = X.shape
+    for t, shape, what in ((s1, (d,), "s1"), (s2, (d, d), "s2")):
+        if t is None:
+            if accumulate:
+                raise L.MGError(f"feature_moments: accumulate needs {what}")
+        elif t.dtype != torch.float64 or tuple(t.shape) != shape or not t.is_cuda or not t.is_contiguous():
+            raise L.MGError(f"feature_moments: {what} must be a contiguous float64 device tensor of {shape}, got "
+                            f"{tuple(t.shape)} {t.dtype} {t.device}")
+    s1 = torch.empty(d, device=X.device, dtype=torch.float64) if s1 is None else s1
+    s2 = torch.empty(d, d, device=X.device, dtype=torch.float64) if s2 is None else s2
+    if work is None:
+        work = torch.empty(moment_segments(max(n, 1), max(d, 1)) * (d * d + d), device=X.device, dtype=torch.float64)
+    call("mg_feature_moments", ptr(X), X.stride(0), n, d, ptr(work), work.numel(), ptr(s1), ptr(s2),
+         1 if accumulate else 0, S())
+    return s1, s2

@@ -610,7 +610,7 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
                      topk=None, dtype=None, process_group=None, seed=0, resume_from=None, save_every_epoch=False,
                      use_graphs=True, on_batch_done=None, text_tokens=False, max_text_tokens=None, clip_grad=False,
                      ema_kimg=None, ema_rampup=0.05, eval_every=None, eval_samples=None, eval_truncation_psi=1.0,
-                     eval_nearest_k=None):
+                     eval_nearest_k=None, eval_frechet=False):
     """Reference :1029-1669.  ``clip_weight_64``/``clip_weight_32`` (the names train_model.py passes,
     SURVEY.md §0) map to the 16x16 / 8x8 CLIP weights.  ``use_amp`` selects bf16 (the MI355X mixed
     precision; the reference's fp16 GradScaler is not needed) unless ``dtype`` is given.
@@ -649,6 +649,9 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
     ``eval_nearest_k`` (None = off; needs ``eval_every``): that evaluation also measures improved precision / recall
     and density / coverage with this many nearest neighbours (moegan_mi.evaluate.prdc), and ``val_precision`` /
     ``val_recall`` / ``val_density`` / ``val_coverage`` join the dict and the logged line.
+    ``eval_frechet`` (off; needs ``eval_every``): that evaluation also measures the Fréchet distance between the
+    generated and the validation images' tower features (moegan_mi.evaluate.frechet_distance), and ``val_fd_clip``
+    joins the dict and the logged line.
     ``resume_from``: a resume checkpoint (:1484-1491 layout, ours or the reference's) to start from;
     ``save_every_epoch``: write that layout after every epoch (the reference's commented-out :1642-1652).
 
@@ -697,6 +700,9 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
             raise ValueError("eval_nearest_k needs eval_every: it adds to that evaluation")
         if eval_nearest_k < 1:
             raise ValueError(f"eval_nearest_k must be a positive number of neighbours, got {eval_nearest_k}")
+    eval_frechet = bool(eval_frechet)
+    if eval_frechet and not eval_every:
+        raise ValueError("eval_frechet needs eval_every: it adds to that evaluation")
     # max_resolution 16 is the reference generator; 32 / 64 / 128 train the progressive extension (layout.py)
     if clip_grad and _clip_model is None:
         raise RuntimeError("clip_grad=True needs the CLIP image tower: call load_clip_weights(path) first")
@@ -815,12 +821,14 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
                 em = evaluate_aurora_gan(generator, val_dataloader, num_samples=eval_samples,
                                          truncation_psi=eval_truncation_psi, seed=seed,
                                          use_ema=generator._store.ema is not None, process_group=process_group,
-                                         nearest_k=eval_nearest_k)
+                                         nearest_k=eval_nearest_k, frechet=eval_frechet)
                 vm.update(val_kid_clip=em["kid_clip"], val_clip_score=em["clip_score"],
                           val_r_precision=em["r_precision"], val_eval_images=em["n"])
                 if eval_nearest_k is not None:
                     vm.update(val_precision=em["precision"], val_recall=em["recall"], val_density=em["density"],
                               val_coverage=em["coverage"])
+                if eval_frechet:
+                    vm.update(val_fd_clip=em["fd_clip"])
                 if rank == 0:
                     print(f"Evaluation ({'EMA' if generator._store.ema is not None else 'live'} generator) - "
                           f"{format_metrics(em)}")
@@ -902,8 +910,8 @@ def _validate(generator, discriminator, loader, gan_loss, temperature_factor, ef
 def evaluate_aurora_gan(generator, dataloader, **kw):
     """KID / CLIP score / R-precision of ``generator`` over the registered image tower's features
     (moegan_mi.evaluate.evaluate_generator; its keywords: num_samples, truncation_psi, seed, use_ema, group,
-    process_group, return_features, and nearest_k, which adds precision / recall / density / coverage).  This
-    build's extension; needs load_clip_weights."""
+    process_group, return_features, nearest_k, which adds precision / recall / density / coverage, and frechet /
+    reference_stats, which add the Fréchet distance 'fd_clip').  This build's extension; needs load_clip_weights."""
     from moegan_mi.evaluate import evaluate_generator
     from moegan_mi.step import clip_tower
     tower = clip_tower(_clip_model)

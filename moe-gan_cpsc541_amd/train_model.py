@@ -115,6 +115,9 @@ def parse_args(argv=None):
     p.add_argument("--eval_nearest_k", type=int, default=None,
                    help="with --eval_every: also improved precision / recall and density / coverage with K nearest "
                         "neighbours (val_precision / val_recall / val_density / val_coverage; default: off)")
+    p.add_argument("--eval_frechet", action="store_true",
+                   help="with --eval_every: also the Fréchet distance between the generated and the validation "
+                        "images' tower features (val_fd_clip; default: off)")
     args = p.parse_args(argv)
     if args.clip_grad and not args.clip_weights:
         p.error("--clip_grad needs --clip_weights (the CLIP image tower whose backward it runs)")
@@ -124,6 +127,8 @@ def parse_args(argv=None):
         p.error("--eval_nearest_k needs --eval_every (the evaluation it adds to)")
     if args.eval_nearest_k is not None and args.eval_nearest_k < 1:
         p.error("--eval_nearest_k must be at least 1")
+    if args.eval_frechet and not args.eval_every:
+        p.error("--eval_frechet needs --eval_every (the evaluation it adds to)")
     return args
 
 
@@ -207,6 +212,8 @@ def main(argv=None):
         kw.setdefault("eval_samples", args.eval_samples)
         if args.eval_nearest_k is not None:
             kw.setdefault("eval_nearest_k", args.eval_nearest_k)
+        if args.eval_frechet:
+            kw.setdefault("eval_frechet", True)
     if kw.get("eval_every"):
         kw.setdefault("eval_truncation_psi", args.eval_truncation_psi)
     G, D = M.train_aurora_gan(train_dl, val_dataloader=val_dl, device=device, save_dir=args.save_dir,
