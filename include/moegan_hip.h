@@ -779,6 +779,34 @@ int mg_manifold_counts(const float* A, int64_t lda, int na, const double* sqA, c
 int mg_feature_moments(const float* X, int64_t ldx, int n, int d, double* work, int64_t nwork, double* s1, double* s2,
                        int accumulate, void* stream);
 
+/* ---- differentiable augmentation of the discriminator's inputs (csrc/mg_augment.hip; no reference counterpart:
+   Zhao et al., "Differentiable Augmentation for Data-Efficient GAN Training") ----
+   A per-image affine map T of a square H x H image with 3 channels, 4 <= H <= 4096, from one row u[0..7] of
+   uniforms in [0, 1) per image (u: fp32 [B, 8]; u[7] is unused).  The steps run in this order, each enabled by a
+   bit of policy_mask:
+     1  brightness   x += u0 - 0.5
+     2  saturation   x = (x - m_p) (2 u1) + m_p,  m_p the mean of the pixel's 3 channels
+     4  contrast     x = (x - M) (u2 + 0.5) + M,  M the mean of the image's 3 H H values after the steps above
+     8  translation  r = round(H / 8) (ties to even), tx = floor(u3 (2 r + 1)) - r, ty likewise from u4;
+                     y[i, j] = x[i + ty, j + tx] (i the row), 0 where the source lies outside the image
+     16 cutout       s = H / 2 (integer), ox = floor(u5 (H + 1 - s % 2)), oy likewise from u6; rows
+                     [oy - s / 2, oy - s / 2 + s) x columns [ox - s / 2, ox - s / 2 + s), clipped, are set to 0
+   The integers are derived in fp32 exactly as written (one fp32 product, floor).  Everything else is fp64: inputs
+   are widened, the two means are fp64 sums in a fixed order, and each output is rounded once (to fp32, then to bf16
+   for a bf16 output), so an fp32 output is within half an ulp (+ fp64 noise) of the exact map, the empty mask copies
+   fp32 bit for bit, and two runs agree bitwise.  One launch per call, one workgroup per image, no atomics, no
+   workspace.  A u outside [0, 1) gives some other shift / cutout but never an access outside the image.
+   mg_diffaug_fwd: x is an image (MG_F32 or MG_BF16) with element strides sb / sh / sw / sc (> 0), as mg_d0_fwd takes
+   them; out is NHWC [B, H, H, ldo] (MG_F32 or MG_BF16, 3 <= ldo <= 64) with channels 3 .. ldo-1 written as 0.
+   mg_diffaug_bwd: out [B, H, H, ldi] = T^T g for g [B, H, H, ldg] (channels < 3 read; 3 .. ldi-1 written as 0): the
+   cutout mask, the shift back, g = c g + (1 - c) mean(g), g = s g + (1 - s) channel-mean(g) with c = u2 + 0.5,
+   s = 2 u1; brightness passes the gradient through.  T is affine, so only u is needed, not the image.
+   Neither call may run in place. */
+int mg_diffaug_fwd(int in_dtype, const void* x, int64_t sb, int64_t sh, int64_t sw, int64_t sc, int B, int H,
+                   const float* u, int policy_mask, int out_dtype, void* out, int64_t ldo, void* stream);
+int mg_diffaug_bwd(int g_dtype, const void* g, int64_t ldg, int B, int H, const float* u, int policy_mask,
+                   int out_dtype, void* out, int64_t ldi, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

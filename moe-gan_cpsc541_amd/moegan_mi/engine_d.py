@@ -185,16 +185,38 @@ class DiscriminatorEngine:
                                     self.G(pre + "weight_v"), self.G(pre + "weight_g")) for pre in WN_LAYERS])
 
     # ------------------------------------------------------------------
-    def d_phase(self, real_nchw, text, fake_img, fake_layout, perm, r1_gamma):
+    def augment(self, img, layout, B, H, u, mask, ld):
+        """T(img) (moegan_mi.augment, ops.diffaug_fwd) as the NHWC [B,H,H,ld] image conv_stack reads, in the compute
+        dtype; ``layout`` as conv_stack takes it."""
+        if layout == "nchw":
+            strides = (3 * H * H, H, 1, H * H)
+        else:
+            strides = (H * H * layout[1], H * layout[1], layout[1], 1)
+        return ops.diffaug_fwd(img, strides, B, H, u, mask, ld, self.cdt)
+
+    def d_phase(self, real_nchw, text, fake_img, fake_layout, perm, r1_gamma, aug_real=None, aug_fake=None,
+                aug_mask=0):
         """D loss + R1 and all D parameter gradients (t2i_moe_gan.py:1276-1326).
         real_nchw [B,3,H,H] fp32; fake_img: generator output (NHWC padded [B,R,R,ld]; R = 16 in the reference).
-        Returns device scalars [d_loss_gan, sp_real, sp_fake, sp_mism] and r1, plus logits."""
+        Returns device scalars [d_loss_gan, sp_real, sp_fake, sp_mism] and r1, plus logits.
+
+        ``aug_real`` / ``aug_fake`` [B,8] with ``aug_mask`` (moegan_mi.augment): the discriminator sees T(real) (NHWC,
+        pitch 4) and T(fake) (the fake's own layout) instead; the mismatched-caption branch shares the real features,
+        so it sees the same T(real).  R1 is taken at the discriminator's input, the augmented real (``r1_grad`` is
+        the gradient there), so the closed form below is unchanged."""
         B = real_nchw.shape[0]
         Hr = real_nchw.shape[-1]
         dev = self.dev
+        if (aug_real is None) != (aug_fake is None):
+            raise ValueError("d_phase: aug_real and aug_fake come together")
+        real_in, real_layout = real_nchw, "nchw"
+        if aug_real is not None:
+            real_in, real_layout = self.augment(real_nchw, "nchw", B, Hr, aug_real, aug_mask, 4), ("nhwc", 4)
+            Hk = fake_img.shape[1]
+            fake_img = self.augment(fake_img, fake_layout, B, Hk, aug_fake, aug_mask, fake_layout[1])
         self.begin_grads()
         t, tb = self.text_branch(text)
-        fr = self.forward(real_nchw, "nchw", text, B, Hr)
+        fr = self.forward(real_in, real_layout, text, B, Hr)
         ff = self.forward(fake_img, fake_layout, text, B, fake_img.shape[1])
         No = fr["img_part"].shape[1]
         out = torch.zeros(4, device=dev)
@@ -257,12 +279,17 @@ class DiscriminatorEngine:
         self.dW["conv_layers.0."] = g.permute(0, 2, 1).contiguous().view(128, 3, 4, 4)
 
     # ------------------------------------------------------------------
-    def g_phase(self, fake_img, fake_layout, text, scale=1.0, want_d_params=False):
+    def g_phase(self, fake_img, fake_layout, text, scale=1.0, want_d_params=False, aug_fake=None, aug_mask=0):
         """Adversarial loss of the generator step (t2i_moe_gan.py:1379-1382) and d loss / d fake image.
         D parameter gradients are formed only when ``want_d_params``: with gradient_accumulation_steps=1 the
-        reference zeroes them before they are ever used (t2i_moe_gan.py:1272 vs :1407)."""
+        reference zeroes them before they are ever used (t2i_moe_gan.py:1272 vs :1407).
+
+        ``aug_fake`` [B,8] with ``aug_mask`` (moegan_mi.augment): the discriminator sees T(fake), and the returned
+        image gradient is T^T of the gradient at its input (ops.diffaug_bwd): d loss / d fake_img."""
         B = fake_img.shape[0]
         Hs = fake_img.shape[1]
+        if aug_fake is not None:
+            fake_img = self.augment(fake_img, fake_layout, B, Hs, aug_fake, aug_mask, fake_layout[1])
         t, tb = self.text_branch(text)
         f = self.forward(fake_img, fake_layout, text, B, Hs)
         No = f["img_part"].shape[1]  # 1 for the reference's 16x16 fakes, (Hs/4-3)^2 for larger ones
@@ -287,6 +314,8 @@ class DiscriminatorEngine:
             self.side.join()
             self._remap_w0()
             self.finish_grads()
+        if aug_fake is not None:
+            g_img = ops.diffaug_bwd(g_img, aug_fake, aug_mask)
         return loss, (fake_pred.view(-1) if No == 1 else fake_pred), g_img
 
     def _text_head_bwd(self, g_tb, t, text):

@@ -20,6 +20,9 @@ FLOAT_KEYS = ("learning_rate", "beta1", "beta2", "r1_gamma", "clip_weight_16", "
               "balance_weight", "ema_kimg", "ema_rampup")
 # this build's switches: "true" / "1" / "yes" / "on" (any case) turn one on, "false" / "0" / "no" / "off" / "" off
 BOOL_KEYS = ("eval_frechet",)
+# this build's policy strings: "" / "none" / "off" / "false" / "0" (any case) mean off (None), anything else is kept
+# (stripped) for the training entry point to validate
+POLICY_KEYS = ("diffaug",)
 # keys of the HPO config that name CLIP weights the training entry point knows under other names
 CLIP_ALIASES = {"clip_weight_64": "clip_weight_16", "clip_weight_32": "clip_weight_8"}
 
@@ -47,6 +50,9 @@ TRAIN_KWARGS = {
     "eval_nearest_k": ("eval_nearest_k", None),
     # ... and, with eval_frechet on, the Fréchet distance over the same features
     "eval_frechet": ("eval_frechet", False),
+    # this build's extension: differentiable augmentation of the discriminator's inputs, a comma-separated subset of
+    # color,translation,cutout (moegan_mi/augment.py); off unless set
+    "diffaug": ("diffaug", None),
 }
 # fixed by the SageMaker entry point (sagemaker_train.py:287-292)
 TRAIN_FIXED = {"log_interval": 100, "save_interval": 500, "gradient_accumulation_steps": 8,
@@ -66,6 +72,15 @@ def _coerce_bool(key, value):
     return bool(value)
 
 
+def _coerce_policy(key, value):
+    if value is None:
+        return None
+    if not isinstance(value, str):
+        raise ValueError(f"{key}: expected a policy string, got {value!r}")
+    v = value.strip()
+    return None if v.lower() in ("", "none", "off", "false", "0") else v
+
+
 def coerce_hyperparameters(raw):
     """sagemaker_train.parse_sagemaker_parameters (:85-102): int / float keys converted, the rest passed as is.
     The HPO config's clip_weight_64 / clip_weight_32 are coerced as floats too (they are CLIP weights)."""
@@ -77,6 +92,8 @@ def coerce_hyperparameters(raw):
             params[key] = float(value)
         elif key in BOOL_KEYS:
             params[key] = _coerce_bool(key, value)
+        elif key in POLICY_KEYS:
+            params[key] = _coerce_policy(key, value)
         else:
             params[key] = value
     return params

@@ -1138,6 +1138,34 @@ def d0_dgrad(g, w0p, out):
     return out
 
 
+def _aug_rows(u, B):
+    if u.dtype != torch.float32 or tuple(u.shape) != (B, 8) or not u.is_contiguous():
+        raise L.MGError(f"diffaug: u must be a contiguous float32 [{B}, 8] tensor, got {tuple(u.shape)} {u.dtype}")
+    return u
+
+
+def diffaug_fwd(x, strides, B, H, u, mask, ldo, dtype):
+    """T(x) (mg_diffaug_fwd): the per-image colour / translation / cutout map of moegan_mi.augment, parameters u
+    [B, 8], steps ``mask``.  x: image with element strides ``strides``; returns NHWC [B, H, H, ldo] in ``dtype`` (pad
+    channels 0)."""
+    out = torch.empty(B, H, H, ldo, device=x.device, dtype=dtype)
+    sb, sh, sw, sc = strides
+    call("mg_diffaug_fwd", dt(x), ptr(x), sb, sh, sw, sc, B, H, ptr(_aug_rows(u, B)), int(mask), dt(out), ptr(out), ldo,
+         S())
+    return out
+
+
+def diffaug_bwd(g, u, mask, ldi=None, dtype=None):
+    """T^T g (mg_diffaug_bwd) for g NHWC [B, H, H, ldg] (contiguous) -> [B, H, H, ldi] in ``dtype`` (default: g's)."""
+    B, H, W, ldg = g.shape
+    if H != W or not g.is_contiguous():
+        raise L.MGError(f"diffaug_bwd: g must be a contiguous square NHWC gradient, got {tuple(g.shape)}")
+    out = torch.empty(B, H, H, ldg if ldi is None else ldi, device=g.device, dtype=g.dtype if dtype is None else dtype)
+    call("mg_diffaug_bwd", dt(g), ptr(g), ldg, B, H, ptr(_aug_rows(u, B)), int(mask), dt(out), ptr(out), out.shape[-1],
+         S())
+    return out
+
+
 def im2col_4x4s2(x, strides, B, H, W, C, Kp, dtype):
     out = torch.empty(B * (H // 2) * (W // 2), Kp, device=x.device, dtype=dtype)
     sb, sh, sw, sc = strides

@@ -53,8 +53,13 @@ class StepConfig:
     def __init__(self, E=4, topk=None, dtype="fp32", r1_gamma=10.0, clip_weight_16=0.1, clip_weight_8=0.05,
                  balance_weight=0.01, beta1=0.5, beta2=0.999, weight_decay=0.01, eps=1e-8, d_clip=0.7, g_clip=0.8,
                  psi=0.7, fp8=False, max_res=16, deterministic=None, clip_grad=False, ema_halflife=None,
-                 ema_rampup=None):
+                 ema_rampup=None, diffaug=None):
         self.E, self.topk = E, topk
+        # differentiable augmentation of the discriminator's inputs (this build's extension, moegan_mi/augment.py): a
+        # policy string, any comma-separated subset of color,translation,cutout; None = off (the reference's step)
+        from .augment import parse_policy
+        self.diffaug = None if diffaug is None else str(diffaug)
+        self.diffaug_mask = None if diffaug is None else parse_policy(diffaug)  # (ValueError for an unknown name)
         # generator output resolution: 16 = the reference; 32 / 64 / 128 = the progressive extension (layout.py)
         self.max_res = max_res
         self.dtype = dtype
@@ -269,9 +274,26 @@ class TrainStep:
             store.mark_shadow_written()
         return ss
 
+    def _check_aug(self, aug, B):
+        """``aug`` is given exactly when the configuration names a policy, as fp32 [3, B, 8] on the step's device."""
+        policy = getattr(self.cfg, "diffaug", None)
+        if policy is None:
+            if aug is not None:
+                raise ValueError("aug was given but StepConfig(diffaug=None): name a policy to augment")
+            return
+        if aug is None:
+            raise ValueError(f"StepConfig(diffaug={policy!r}) needs the step's aug [3, {B}, 8] "
+                             "(moegan_mi.augment.draw)")
+        if not torch.is_tensor(aug) or aug.dtype != torch.float32 or tuple(aug.shape) != (3, B, 8):
+            got = (tuple(aug.shape), aug.dtype) if torch.is_tensor(aug) else type(aug).__name__
+            raise ValueError(f"aug must be a float32 [3, {B}, 8] tensor, got {got}")
+        if aug.device.type != self.dev.type or not aug.is_contiguous():
+            raise ValueError(f"aug must be contiguous on {self.dev}, got {aug.device}")
+
     # ---- the step ----
     def step(self, real, text, z, eps_d, eps_g, perm, *, anneal=3.0, lr_g=2e-4, lr_d=2e-4, eff_kl_weight=1e-8,
-             prep=True, acc=1, zero_grads=True, step_optim=True, text_rows=None, row_off=None, lk_max=None):
+             prep=True, acc=1, zero_grads=True, step_optim=True, text_rows=None, row_off=None, lk_max=None,
+             aug=None):
         """real [B,3,64,64] fp32 NCHW, text [B,512], z [B,512] fp32 (device); eps_d / eps_g: 3 triples of
         router epsilon tensors; perm [B] int32.  Returns a dict of device tensors.
 
@@ -284,7 +306,14 @@ class TrainStep:
         Gradient accumulation (t2i_moe_gan.py:1272, :1329, :1353, :1413): ``zero_grads`` at the first batch of
         a window, ``step_optim`` at its last; gradients are summed and scaled by 1/acc before clipping.  As in
         the reference, the generator step's loss also accumulates into the discriminator's gradients, which
-        matters only when the D optimizer has not stepped yet in the window (acc > 1)."""
+        matters only when the D optimizer has not stepped yet in the window (acc > 1).
+
+        ``aug`` fp32 [3,B,8] (device; moegan_mi.augment.draw), required exactly when ``cfg.diffaug`` names a policy:
+        the discriminator sees T(image) wherever it sees an image -- row 0 transforms the real batch of the D phase
+        (the mismatched-caption branch shares those features), row 1 the fakes of the D phase, row 2 the fakes of the
+        G phase, whose image gradient comes back through T^T.  R1 is taken at the discriminator's input (the
+        augmented real); the CLIP terms and the returned images stay un-augmented."""
+        self._check_aug(aug, real.shape[0])
         if self.clip_grad and self._clip_tower is None:
             raise ValueError("clip_grad=True: attach the image tower first (TrainStep(..., clip_encoder=tower))")
         ops.ARENA.begin(self.dev)
@@ -297,7 +326,7 @@ class TrainStep:
         x3_prev = ops.set_f32x3(self.cdt == torch.bfloat16 and os.environ.get("MOEGAN_F32X3", "1") == "1")
         try:
             return self._step(real, text, z, eps_d, eps_g, perm, anneal, lr_g, lr_d, eff_kl_weight, prep, acc,
-                              zero_grads, step_optim, text_rows, row_off, lk_max)
+                              zero_grads, step_optim, text_rows, row_off, lk_max, aug)
         finally:
             ops.fold_defer(False)
             ops.set_f32x3(x3_prev)
@@ -307,8 +336,11 @@ class TrainStep:
             self.ge.guard_flags = None
 
     def _step(self, real, text, z, eps_d, eps_g, perm, anneal, lr_g, lr_d, eff_kl_weight, prep, acc, zero_grads,
-              step_optim, text_rows=None, row_off=None, lk_max=None):
+              step_optim, text_rows=None, row_off=None, lk_max=None, aug=None):
         c = self.cfg
+        aug_mask = getattr(c, "diffaug_mask", None) or 0
+        aug_d = dict(aug_real=aug[0], aug_fake=aug[1], aug_mask=aug_mask) if aug is not None else {}
+        aug_g = dict(aug_fake=aug[2], aug_mask=aug_mask) if aug is not None else {}
         accum = acc > 1
         gs, ds = self.gs, self.ds
         flags = ops.zeros(1, device=self.dev, dtype=torch.int32)  # the step's guard word (zero arena)
@@ -330,7 +362,7 @@ class TrainStep:
                                                         want_kl=False, keep_prefix=True, text_rows=text_rows,
                                                         row_off=row_off, lk_max=lk_max)
         prefix, self.ge.last_prefix = self.ge.last_prefix, None
-        dres = self.de.d_phase(real, text, f16, ("nhwc", 8), perm, c.r1_gamma)
+        dres = self.de.d_phase(real, text, f16, ("nhwc", 8), perm, c.r1_gamma, **aug_d)
         ops.fold_flush()
         ops.COLSUMS.flush()
         # guard: NaN / Inf d_loss skips the whole batch (t2i_moe_gan.py:1315-1320)
@@ -359,7 +391,7 @@ class TrainStep:
         leak = accum and not step_optim  # the G loss also reaches D's gradients while D has not stepped yet
         if leak:
             ds.zero_grad()
-        g_gan, fake_pred, g_img = self.de.g_phase(img16, ("nhwc", 8), text, want_d_params=leak)
+        g_gan, fake_pred, g_img = self.de.g_phase(img16, ("nhwc", 8), text, want_d_params=leak, **aug_g)
         ops.fold_flush()
         ops.COLSUMS.flush()
         # balance loss on the last MoE layer, over the GLOBAL batch (t2i_moe_gan.py:951-1000)

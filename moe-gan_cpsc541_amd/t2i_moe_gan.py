@@ -510,7 +510,10 @@ class _StepRunner:
 
     A token batch (``text_rows`` / ``row_off`` / ``lk_max``, moegan_mi.tokens) adds its two buckets (rows, lk_max)
     to the variant key, with static buffers for the packed rows and the offsets.  At most ``MAX_TOKEN_VARIANTS``
-    token variants are kept per epoch; a batch that would need one more runs eagerly."""
+    token variants are kept per epoch; a batch that would need one more runs eagerly.
+
+    ``aug`` (the augmentation parameters of StepConfig.diffaug, [3, B, 8]) is an input like ``perm``: a static buffer
+    per variant, refilled before every replay."""
 
     MAX_TOKEN_VARIANTS = 8
 
@@ -536,7 +539,7 @@ class _StepRunner:
             self.pool = None  # (a released pool cannot be captured into again: the next capture makes a new one)
             self.epoch_key = ekey
         key = (kw.get("zero_grads", True), kw.get("step_optim", True))
-        text_rows, row_off = kw.get("text_rows"), kw.get("row_off")
+        text_rows, row_off, aug = kw.get("text_rows"), kw.get("row_off"), kw.get("aug")
         if text_rows is not None:
             key += (int(text_rows.shape[0]), int(kw["lk_max"]))
         ent = self.graphs.get(key)
@@ -549,6 +552,9 @@ class _StepRunner:
             if text_rows is not None:
                 bufs.update(text_rows=text_rows.clone(), row_off=row_off.clone())
                 kws.update(text_rows=bufs["text_rows"], row_off=bufs["row_off"])
+            if aug is not None:
+                bufs.update(aug=aug.clone())
+                kws.update(aug=bufs["aug"])
 
             def fn(b=bufs, kw=kws):
                 return self.ts.step(b["real"], b["text"], b["z"], b["eps_d"], b["eps_g"], b["perm"], **kw)
@@ -569,6 +575,8 @@ class _StepRunner:
             if text_rows is not None:
                 b["text_rows"].copy_(text_rows)
                 b["row_off"].copy_(row_off)
+            if aug is not None:
+                b["aug"].copy_(aug)
             for dst, src in zip(b["eps_d"], eps_d):
                 for x, y in zip(dst, src):
                     x.copy_(y)
@@ -610,7 +618,7 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
                      topk=None, dtype=None, process_group=None, seed=0, resume_from=None, save_every_epoch=False,
                      use_graphs=True, on_batch_done=None, text_tokens=False, max_text_tokens=None, clip_grad=False,
                      ema_kimg=None, ema_rampup=0.05, eval_every=None, eval_samples=None, eval_truncation_psi=1.0,
-                     eval_nearest_k=None, eval_frechet=False):
+                     eval_nearest_k=None, eval_frechet=False, diffaug=None):
     """Reference :1029-1669.  ``clip_weight_64``/``clip_weight_32`` (the names train_model.py passes,
     SURVEY.md §0) map to the 16x16 / 8x8 CLIP weights.  ``use_amp`` selects bf16 (the MI355X mixed
     precision; the reference's fp16 GradScaler is not needed) unless ``dtype`` is given.
@@ -652,6 +660,11 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
     ``eval_frechet`` (off; needs ``eval_every``): that evaluation also measures the Fréchet distance between the
     generated and the validation images' tower features (moegan_mi.evaluate.frechet_distance), and ``val_fd_clip``
     joins the dict and the logged line.
+    ``diffaug`` (this build's extension; None = off, the reference's loop): a differentiable-augmentation policy, any
+    comma-separated subset of ``color,translation,cutout`` (moegan_mi.augment): every image the discriminator sees in
+    a training step, real and fake, goes through a random colour / shift / cutout transform whose parameters are
+    drawn per batch from the per-rank generator -- only when the feature is on, so the default random streams and
+    resume files are unchanged.  Validation, evaluation, sampling and the CLIP terms see un-augmented images.
     ``resume_from``: a resume checkpoint (:1484-1491 layout, ours or the reference's) to start from;
     ``save_every_epoch``: write that layout after every epoch (the reference's commented-out :1642-1652).
 
@@ -661,6 +674,9 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
     the same preallocated step (one hipGraph per variant), so its memory is fixed before the first batch: a
     per-batch check would give the same answer for every batch, and with 288 GB of HBM per GPU the C2 step fits
     many times over.  The loop logs the step's allocated memory against the limit once, after the first batch."""
+    if diffaug is not None:
+        from moegan_mi.augment import parse_policy
+        parse_policy(diffaug)  # an unknown name is an error before anything is created or built
     os.makedirs(save_dir, exist_ok=True)
     if clip_weight_64 is not None:
         clip_weight_16 = clip_weight_64
@@ -714,7 +730,7 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
     cfg = StepConfig(E=num_experts, topk=topk, dtype=dtype, r1_gamma=r1_gamma, clip_weight_16=clip_weight_16,
                      clip_weight_8=clip_weight_8, balance_weight=balance_weight, beta1=beta1, beta2=beta2,
                      max_res=max_resolution, clip_grad=clip_grad, ema_halflife=ema_halflife,
-                     ema_rampup=float(ema_rampup) if ema_rampup is not None else None)
+                     ema_rampup=float(ema_rampup) if ema_rampup is not None else None, diffaug=diffaug)
     # CLIP terms of the generator loss (logging / guard only unless clip_grad: no gradient, :98-101)
     ts = TrainStep(cfg, device, process_group=process_group, gstore=generator._store, dstore=discriminator._store,
                    clip_encoder=_clip_model.encode_image if _clip_model is not None else None)
@@ -794,10 +810,14 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
             eps_d = [tuple(t.clone() for t in trip) for trip in _eps_for(generator._store, g_shared)]
             eps_g = _eps_for(generator._store, g_shared)
             perm = torch.randperm(B, device=device, generator=g_local).int()
+            aug_kw = {}
+            if diffaug is not None:  # (drawn only when on: the default streams stay as they were)
+                from moegan_mi.augment import draw
+                aug_kw = dict(aug=draw(B, g_local))
             zero = batch_idx % acc == 0
             stp = (batch_idx + 1) % acc == 0 or (batch_idx + 1) == n_batches
             out = runner(real, text, z, eps_d, eps_g, perm, anneal=temperature_factor, lr_g=cur_lr, lr_d=cur_lr,
-                         eff_kl_weight=eff_kl, acc=acc, zero_grads=zero, step_optim=stp, **tok_kw)
+                         eff_kl_weight=eff_kl, acc=acc, zero_grads=zero, step_optim=stp, **tok_kw, **aug_kw)
             if device.type == "cuda":
                 rec = _stats_to_host(out) + (batch_idx,)
             else:

@@ -118,7 +118,16 @@ def parse_args(argv=None):
     p.add_argument("--eval_frechet", action="store_true",
                    help="with --eval_every: also the Fréchet distance between the generated and the validation "
                         "images' tower features (val_fd_clip; default: off)")
+    p.add_argument("--diffaug", type=str, default=None, metavar="POLICY",
+                   help="differentiable augmentation of every image the discriminator sees, real and fake: a "
+                        "comma-separated subset of color,translation,cutout (default: off)")
     args = p.parse_args(argv)
+    if args.diffaug is not None:
+        from moegan_mi.augment import parse_policy
+        try:
+            parse_policy(args.diffaug)
+        except ValueError as e:
+            p.error(f"--diffaug: {e}")
     if args.clip_grad and not args.clip_weights:
         p.error("--clip_grad needs --clip_weights (the CLIP image tower whose backward it runs)")
     if args.eval_every and not args.clip_weights:
@@ -214,6 +223,8 @@ def main(argv=None):
             kw.setdefault("eval_nearest_k", args.eval_nearest_k)
         if args.eval_frechet:
             kw.setdefault("eval_frechet", True)
+    if args.diffaug is not None:
+        kw.setdefault("diffaug", args.diffaug)
     if kw.get("eval_every"):
         kw.setdefault("eval_truncation_psi", args.eval_truncation_psi)
     G, D = M.train_aurora_gan(train_dl, val_dataloader=val_dl, device=device, save_dir=args.save_dir,
