@@ -798,28 +798,7 @@ struct Grouping {
 // transpose delivers 4 k-rows of one column per lane).  The MC row pitch is an odd multiple of 16
 // dwords and columns are XOR-swizzled by 16 elements on odd k-octets, so both halves of a wave's
 // transposed read (k-rows 8g..8g+3 for lane groups g = 0, 1) hit 8 distinct bank octets.
-template <typename T> struct Tile;
-template <> struct Tile<bf16_t> { static constexpr int BK = 64, PADK = 0, PADM = 32; };
-template <> struct Tile<float> { static constexpr int BK = 32, PADK = 4, PADM = 16; };
-
-// K step of a GEMM instantiation: X3 (fp32 operands multiplied as split bf16, hi*hi + hi*lo + lo*hi) stages its
-// tiles as bf16 images, so it takes the bf16 step
-// MG_BK_SMALL: the K step of bf16 tiles of at most 64 x 64 outputs (A/B build switch; 64 = the common step).  A
-// 128-deep step doubles the bytes each of those latency-bound blocks keeps in flight per barrier.
-#ifndef MG_BK_SMALL
-#define MG_BK_SMALL 64
-#endif
-// MG_X3_BK: the K step of the split-bf16 fp32 tiles (64 x 64 only; the small-M prefix / demodulation GEMMs are
-// serial chains of K steps on few tiles, so a deeper step halves their chain; 64 = the bf16 step)
-#ifndef MG_X3_BK
-#define MG_X3_BK 64
-#endif
-template <typename T, bool X3, int BM = 128, int BN = 128> constexpr int tile_bk() {
-  return X3 ? (BM * BN <= 64 * 64 ? MG_X3_BK : Tile<bf16_t>::BK)
-            : (sizeof(T) == 2 && BM * BN <= 64 * 64) ? MG_BK_SMALL : Tile<T>::BK;
-}
-// the largest K step any bf16 tile uses (the implicit-conv loaders' "one tap per K step" test needs Cin >= it)
-template <typename T> constexpr int max_tile_bk() { return tile_bk<T, false, 64, 64>() > Tile<T>::BK ? tile_bk<T, false, 64, 64>() : Tile<T>::BK; }
+// (Tile<T>: BK / PADK / PADM, and the K step of an instantiation, tile_bk: mg_plan.h)
 
 template <typename T> MG_DEV constexpr int mc_swz(int k) { return sizeof(T) == 2 ? ((k >> 3) & 1) << 4 : 0; }
 // KC image element offset of (row r, k) for bf16: 16-B chunk (k / 8) stored at chunk (k / 8) ^ (r & 7)

@@ -82,68 +82,30 @@ void run_plain_orient(int a_kc, int b_kc, int M, int N, int K, const void* A, in
   else run_plain<T, TO, BM, BN, false, false, XF, X3>(M, N, K, A, lda, B, ldb, C, ldc, e, splits, st);
 }
 
-template <typename T, typename TO, bool X3 = false>
-void run_plain_tiles(int a_kc, int b_kc, int M, int N, int K, const void* A, int64_t lda, const void* B,
-                     int64_t ldb, void* C, int64_t ldc, const mg_epilogue* e, int splits, hipStream_t st) {
-  if constexpr (X3) {  // split-bf16 fp32 GEMMs (small-M prefix / demodulation products): 64x64 tiles only
+// one launch on the plan's tile (the one-launch tile of a slab plan whose workspace could not be had)
+template <typename T, typename TO, bool X3>
+void run_plain_tiles(int BM, int BN, int a_kc, int b_kc, int M, int N, int K, const void* A, int64_t lda,
+                     const void* B, int64_t ldb, void* C, int64_t ldc, const mg_epilogue* e, int splits, hipStream_t st) {
+  if constexpr (X3) {
     if (a_xf(e)) run_plain_orient<T, TO, 64, 64, true, true>(a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, e, splits, st);
     else run_plain_orient<T, TO, 64, 64, false, true>(a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, e, splits, st);
     return;
   }
-  if (a_xf(e)) {  // loader transforms: generic 64x64 instantiation
-    run_plain_orient<T, TO, 64, 64, true>(a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, e, splits, st);
-    return;
-  }
-  const int tile = g_mg_tune[MG_TUNE_GEMM_TILE];
-  // one K step (K <= BK: the D head GEMMs, K = 16 / 48): 64^2 tiles keep more blocks in flight (9.46 -> 9.44 ms per
-  // step, A/B MG_TUNE_SHORTK = 2 restores the size rule below)
-  if (tile == 0 && K <= Tile<T>::BK && g_mg_tune[MG_TUNE_SHORTK] != 2) {
-    run_plain_orient<T, TO, 64, 64>(a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, e, splits, st);
-    return;
-  }
-  // short K over many rows (the token projections, K = 128 / 256 at 16K-64K rows): each tile's K loop is one or two
-  // steps, so it is bound by load latency and more, smaller tiles keep more bytes in flight (measured at the C2
-  // shapes: 65536 x 256 x 128 26.5 -> 15.7 us, 65536 x 384 x 128 28.5 -> 22.5 us on 64^2;
-  // profiles/round4_shortk_probe.txt)
-  if (tile == 0 && K <= 256 && M >= 16384) {
-    run_plain_orient<T, TO, 64, 64>(a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, e, splits, st);
-    return;
-  }
+  if (a_xf(e)) return run_plain_orient<T, TO, 64, 64, true>(a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, e, splits, st);
+  if (BM == 64) return run_plain_orient<T, TO, 64, 64>(a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, e, splits, st);
   if constexpr (sizeof(T) == 2) {
-    // 128 x 256 when N fills it and the grid covers the chip (measured: 4096^3 bf16 816 -> 920 TF/s;
-    // the step's few-tile projections stay on 128^2 / 64^2)
-    if (tile == 257 || (tile == 0 && N % 256 == 0 && (int64_t)cdiv(M, 128) * (N / 256) * splits >= 480)) {
-      run_plain_orient<T, TO, 128, 256>(a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, e, splits, st);
-      return;
-    }
+    if (BN == 256) return run_plain_orient<T, TO, 128, 256>(a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, e, splits, st);
   }
-  if (tile == 128 || (tile == 0 && (int64_t)cdiv(M, 128) * cdiv(N, 128) * splits >= 480))
-    run_plain_orient<T, TO, 128, 128>(a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, e, splits, st);
-  else
-    run_plain_orient<T, TO, 64, 64>(a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, e, splits, st);
+  run_plain_orient<T, TO, 128, 128>(a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, e, splits, st);
 }
 
-// Few-tile GEMMs (styles, mapping, router/attention projections at small M) are latency-bound: a
-// 64x64 grid of ~32 blocks walks K serially.  Split K over ~256 blocks into fp32 slabs and apply
-// the real epilogue in a reduction pass.  Returns false when the shape does not qualify.
-// ``want_splits`` > 0 (deterministic mode, an atomic split-K epilogue): exactly that many slabs, any tile count;
-// the reduction pass then adds each output element once.
-template <typename T, typename TO, bool X3 = false>
-bool run_splitk_slabs(int a_kc, int b_kc, int M, int N, int K, const void* A, int64_t lda, const void* B,
-                      int64_t ldb, void* C, int64_t ldc, const mg_epilogue* e, hipStream_t st, int want_splits = 0) {
-  constexpr int TBK = tile_bk<T, X3, 64, 64>();
-  int64_t tiles = (int64_t)cdiv(M, 64) * cdiv(N, 64);
-  if (a_xf(e)) return false;
-  int splits;
-  if (want_splits > 0) {
-    splits = std::max(1, std::min(want_splits, cdiv(K, TBK)));
-  } else {
-    if (tiles >= 96 || K < 4 * TBK) return false;
-    splits = (int)std::min<int64_t>(256 / tiles, K / (2 * TBK));
-  }
-  if (splits < 2) return false;
-  int kchunk = ((K + splits - 1) / splits + TBK - 1) / TBK * TBK;
-  splits = (K + kchunk - 1) / kchunk;
+// A slab plan: p.splits fp32 slabs of p.kchunk on 64^2 tiles, the real epilogue in the reduction pass (which adds
+// each output element once, in split order).  False when the workspace cannot be had.
+template <typename T, typename TO, bool X3>
+bool run_splitk_slabs(const Plan& p, int a_kc, int b_kc, int M, int N, int K, const void* A, int64_t lda,
+                      const void* B, int64_t ldb, void* C, int64_t ldc, const mg_epilogue* e, hipStream_t st) {
+  const int splits = p.splits, kchunk = p.kchunk;
+  const int64_t tiles = (int64_t)cdiv(M, 64) * cdiv(N, 64);
   const int64_t MN = (int64_t)M * N;
   float* ws = reinterpret_cast<float*>(mg_workspace((size_t)splits * MN * sizeof(float), st));
   if (!ws) return false;
@@ -220,58 +182,21 @@ extern "C" int mg_gemm(int dtype, int M, int N, int K, const void* A, int64_t ld
       mg_wgrad_wide(M, N, K, A, lda, B, ldb, reinterpret_cast<float*>(C), ldc, ep->alpha,
                     reinterpret_cast<hipStream_t>(stream)))
     return mg_check_launch("mg_gemm (wide weight gradient)");
-  if (splits < 1) {  // auto split-K (atomic fp32 epilogues only): ~512 blocks, >= 256 of K per split
-    if (ep && ep->atomic) {
-      int64_t tiles = (int64_t)cdiv(M, 64) * cdiv(N, 64);
-      const int target = g_mg_tune[MG_TUNE_ATOMIC_BLOCKS] > 0 ? (int)g_mg_tune[MG_TUNE_ATOMIC_BLOCKS] : 512;
-      int64_t want = std::max<int64_t>(1, target / std::max<int64_t>(tiles, 1));
-      // the least K per split: 256 (one bf16 128-deep step pair), or the tuned value (A/B: a few-tile fp32 weight
-      // gradient at K = B = 256 rows otherwise walks its 4 K steps serially on 64 blocks)
-      const int mink = g_mg_tune[MG_TUNE_ATOMIC_MINK] > 0 ? (int)g_mg_tune[MG_TUNE_ATOMIC_MINK] : 256;
-      splits = (int)std::max<int64_t>(1, std::min<int64_t>(want, K / mink));
-    } else {
-      splits = 1;
-    }
-  }
-  MG_REQUIRE(splits == 1 || (ep && ep->atomic && c_dtype == MG_F32), "split-K requires an atomic fp32 epilogue");
-  MG_REQUIRE(!(ep && ep->atomic) || c_dtype == MG_F32, "atomic epilogue requires fp32 C");
-  if (K == 0) splits = 1;
+  const bool atomic = ep && ep->atomic;
+  MG_REQUIRE(splits <= 1 || (atomic && c_dtype == MG_F32), "split-K requires an atomic fp32 epilogue");
+  MG_REQUIRE(!atomic || c_dtype == MG_F32, "atomic epilogue requires fp32 C");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (splits > 1 && mg_det()) {  // deterministic mode: fp32 slabs + one fixed-order reduction, not atomics
-    bool done;
-    if (x3)
-      done = run_splitk_slabs<float, float, true>(a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, ep, st, splits);
-    else if (dtype == MG_F32)
-      done = run_splitk_slabs<float, float>(a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, ep, st, splits);
-    else
-      done = run_splitk_slabs<bf16_t, float>(a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, ep, st, splits);
-    if (done) return mg_check_launch("mg_gemm (deterministic split-K slabs)");
-    splits = 1;
-  }
-  if (splits == 1 && !(ep && ep->atomic) && !qgg && !g_mg_tune[MG_TUNE_NO_SLABS]) {
-    bool done;
-    if (x3)
-      done = c_dtype == MG_F32 ? run_splitk_slabs<float, float, true>(a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, ep, st)
-                               : run_splitk_slabs<float, bf16_t, true>(a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, ep, st);
-    else if (dtype == MG_F32)
-      done = c_dtype == MG_F32 ? run_splitk_slabs<float, float>(a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, ep, st)
-                               : run_splitk_slabs<float, bf16_t>(a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, ep, st);
-    else
-      done = c_dtype == MG_F32 ? run_splitk_slabs<bf16_t, float>(a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, ep, st)
-                               : run_splitk_slabs<bf16_t, bf16_t>(a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, ep, st);
-    if (done) return mg_check_launch("mg_gemm (split-K slabs)");
-  }
-  if (x3) {
-    if (c_dtype == MG_F32) run_plain_tiles<float, float, true>(a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, ep, splits, st);
-    else run_plain_tiles<float, bf16_t, true>(a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, ep, splits, st);
-  } else if (dtype == MG_F32) {
-    if (c_dtype == MG_F32) run_plain_tiles<float, float>(a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, ep, splits, st);
-    else run_plain_tiles<float, bf16_t>(a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, ep, splits, st);
-  } else {
-    if (c_dtype == MG_F32) run_plain_tiles<bf16_t, float>(a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, ep, splits, st);
-    else run_plain_tiles<bf16_t, bf16_t>(a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, ep, splits, st);
-  }
-  return mg_check_launch("mg_gemm");
+  const Plan p = plan_gemm(dtype == MG_BF16, x3, M, N, K, GemmEpi{atomic, a_xf(ep), qgg}, splits);
+  return with_types(x3, dtype, c_dtype, [&](auto t, auto to, auto x3c) {
+    using T = decltype(t);
+    using TO = decltype(to);
+    if (p.route == ROUTE_SLABS &&
+        run_splitk_slabs<T, TO, decltype(x3c)::value>(p, a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, ep, st))
+      return mg_check_launch(atomic ? "mg_gemm (deterministic split-K slabs)" : "mg_gemm (split-K slabs)");
+    run_plain_tiles<T, TO, decltype(x3c)::value>(p.fb_BM, p.fb_BN, a_kc, b_kc, M, N, K, A, lda, B, ldb, C, ldc, ep,
+                                                 p.route == ROUTE_SLABS ? 1 : p.splits, st);
+    return mg_check_launch("mg_gemm");
+  });
 }
 
 // Linear-layer weight gradient C[M][N] += alpha * sum_k A[k][m] B[k][n] (mg_gemm with a_kc = b_kc = 0, bf16 operands and
@@ -294,27 +219,18 @@ extern "C" int mg_gemm_wgrad_bias(int dtype, int M, int N, int K, const void* A,
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   if (splits < 1 && mg_wgrad_wide(M, N, K, A, lda, B, ldb, C, ldc, alpha, st, bias_out))
     return mg_check_launch("mg_gemm_wgrad_bias (wide weight gradient)");
-  if (splits < 1) {  // mg_gemm's rule for atomic epilogues
-    const int64_t tiles = (int64_t)cdiv(M, 64) * cdiv(N, 64);
-    const int target = g_mg_tune[MG_TUNE_ATOMIC_BLOCKS] > 0 ? (int)g_mg_tune[MG_TUNE_ATOMIC_BLOCKS] : 512;
-    const int64_t want = std::max<int64_t>(1, target / std::max<int64_t>(tiles, 1));
-    const int mink = g_mg_tune[MG_TUNE_ATOMIC_MINK] > 0 ? (int)g_mg_tune[MG_TUNE_ATOMIC_MINK] : 256;
-    splits = (int)std::max<int64_t>(1, std::min<int64_t>(want, K / mink));
-  }
-  if (K == 0) splits = 1;
+  // mg_gemm's plan for this call: tiles meeting in atomics (deterministic mode is refused above)
+  const Plan p = plan_gemm(true, false, M, N, K, GemmEpi{true, false, false}, splits);
   mg_epilogue e{};
   e.alpha = alpha;
   e.atomic = 1;
   auto ep = with_bias_grad(make_epi<float>(C, ldc, &e), bias_out, 0);
   LdMC<bf16_t> la{reinterpret_cast<const bf16_t*>(A), lda, M, K, nullptr, 1, nullptr, 0};
   LdMC<bf16_t> lb{reinterpret_cast<const bf16_t*>(B), ldb, N, K, nullptr, 1, nullptr, 0};
-  // run_plain_tiles' tile rule (its 128 x 256 tile is not built with the bias sum: 128^2 there)
-  const int tile = g_mg_tune[MG_TUNE_GEMM_TILE];
-  const bool small = tile == 0 && ((K <= Tile<bf16_t>::BK && g_mg_tune[MG_TUNE_SHORTK] != 2) || (K <= 256 && M >= 16384));
-  if (!small && (tile == 128 || tile == 257 || (tile == 0 && (int64_t)cdiv(M, 128) * cdiv(N, 128) * splits >= 480)))
-    launch_gemm<bf16_t, 128, 128, false, false>(la, lb, ep, M, N, K, splits, kNoGroup, 0, st);
+  if (p.BM == 128)  // (the 128 x 256 tile is not built with the bias sum: 128^2 there)
+    launch_gemm<bf16_t, 128, 128, false, false>(la, lb, ep, M, N, K, p.splits, kNoGroup, 0, st);
   else
-    launch_gemm<bf16_t, 64, 64, false, false>(la, lb, ep, M, N, K, splits, kNoGroup, 0, st);
+    launch_gemm<bf16_t, 64, 64, false, false>(la, lb, ep, M, N, K, p.splits, kNoGroup, 0, st);
   return mg_check_launch("mg_gemm_wgrad_bias");
 }
 
@@ -455,23 +371,15 @@ void run_conv(const void* x, int B, int H, int W, int Cin, const void* wpack, in
   auto ep = make_epi<TO>(y, ldy, e);
   launch_gemm<T, BM, BN, true, true>(la, lb, ep, M, Cout, K, 1, kNoGroup, 0, st);
 }
-// Implicit conv with few output tiles for its K (the MTM offset heads, Cout = 32, K = 9*Cin up to 4608; the 4x4
-// 512 -> 512 convs, 512 tiles of 72 K steps) walks K serially in too few blocks to hide load latency: split K into
-// fp32 slabs over ~1024 blocks of >= 8 K steps each and apply the epilogue in the reduction.  Narrow outputs
-// (Cout <= 32) use 128 x 32 tiles (no MFMA columns wasted).
+// A slab plan: p.splits fp32 slabs of p.kchunk on the plan's BM x BN tile, the epilogue in the reduction.  False when
+// the workspace cannot be had.
 template <typename T, typename TO, bool SC, int BM, int BN>
-bool conv_slabs_t(const void* x, int B, int H, int W, int Cin, const void* wpack, int Cout, int KH, int KW,
-                  int stride, int pad, const float* sc, void* y, int64_t ldy, const mg_epilogue* e, hipStream_t st) {
-  constexpr int TBK = tile_bk<T, false, BM, BN>();
+bool conv_slabs_t(const Plan& p, const void* x, int B, int H, int W, int Cin, const void* wpack, int Cout, int KH,
+                  int KW, int stride, int pad, void* y, int64_t ldy, const mg_epilogue* e, hipStream_t st) {
   int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
   int M = B * OH * OW, K = KH * KW * Cin;
   int64_t tiles = (int64_t)cdiv(M, BM) * cdiv(Cout, BN);
-  const int ksteps = K / TBK;
-  if (tiles >= 1024 || ksteps < 16 || (e && e->atomic) || sc || g_mg_tune[MG_TUNE_NO_SLABS]) return false;
-  int splits = (int)std::min<int64_t>(cdiv(1024, tiles), ksteps / 8);
-  if (splits < 2) return false;
-  int kchunk = ((K + splits - 1) / splits + TBK - 1) / TBK * TBK;
-  splits = (K + kchunk - 1) / kchunk;
+  const int splits = p.splits, kchunk = p.kchunk;
   const int64_t MN = (int64_t)M * Cout;
   float* ws = reinterpret_cast<float*>(mg_workspace((size_t)splits * MN * sizeof(float), st));
   if (!ws) return false;
@@ -481,7 +389,7 @@ bool conv_slabs_t(const void* x, int B, int H, int W, int Cin, const void* wpack
   slab.zstride = MN;
   slab.vec_ok = slab.host_vec_ok() ? 1 : 0;
   LdKCConv<T, false, SC> la{reinterpret_cast<const T*>(x), H, W, Cin, ilog2(Cin), ilog2(OW), ilog2(OH * OW), M,
-                            KW, stride, pad, K, sc, kwinv(KW)};
+                            KW, stride, pad, K, nullptr, kwinv(KW)};
   LdKC<T> lb{reinterpret_cast<const T*>(wpack), K, Cout, K, nullptr, 1, nullptr, 0};
   dim3 grid(cdiv(M, BM), cdiv(Cout, BN), splits);
   auto ep = make_epi<TO>(y, ldy, e);
@@ -500,75 +408,37 @@ bool conv_slabs_t(const void* x, int B, int H, int W, int Cin, const void* wpack
 }
 
 template <typename T, typename TO, bool SC>
-bool conv_slabs(const void* x, int B, int H, int W, int Cin, const void* wpack, int Cout, int KH, int KW, int stride,
-                int pad, const float* sc, void* y, int64_t ldy, const mg_epilogue* e, hipStream_t st) {
+bool conv_slabs(const Plan& p, const void* x, int B, int H, int W, int Cin, const void* wpack, int Cout, int KH,
+                int KW, int stride, int pad, void* y, int64_t ldy, const mg_epilogue* e, hipStream_t st) {
   if constexpr (sizeof(T) == 2) {
-    if (Cout <= 32)
-      return conv_slabs_t<T, TO, SC, 128, 32>(x, B, H, W, Cin, wpack, Cout, KH, KW, stride, pad, sc, y, ldy, e, st);
+    if (p.BN == 32)
+      return conv_slabs_t<T, TO, SC, 128, 32>(p, x, B, H, W, Cin, wpack, Cout, KH, KW, stride, pad, y, ldy, e, st);
   }
-  return conv_slabs_t<T, TO, SC, 64, 64>(x, B, H, W, Cin, wpack, Cout, KH, KW, stride, pad, sc, y, ldy, e, st);
+  return conv_slabs_t<T, TO, SC, 64, 64>(p, x, B, H, W, Cin, wpack, Cout, KH, KW, stride, pad, y, ldy, e, st);
 }
 
+// one launch on a BM x BN tile the plan chose (plan_conv_fwd: the tiles it names are the ones built here)
 template <typename T, typename TO>
-void run_conv_tiles(const void* x, int B, int H, int W, int Cin, const void* wpack, int Cout, int KH, int KW,
-                    int stride, int pad, const float* sc, void* y, int64_t ldy, const mg_epilogue* e,
-                    hipStream_t st) {
-  if constexpr (sizeof(T) == 2) {  // 32-channel 3x3 convs on small maps (offset heads): direct, halo tiles in LDS
-    if (!sc && mg_conv3_direct_ok(H, W, Cin, Cout, KH, KW, stride, pad, false) &&
-        mg_conv3_direct(x, B, H, Cin, wpack, Cout, e, y, ldy, std::is_same<TO, float>::value ? MG_F32 : MG_BF16, st))
-      return;
+void run_conv_tiles(int BM, int BN, bool small_c, const void* x, int B, int H, int W, int Cin, const void* wpack,
+                    int Cout, int KH, int KW, int stride, int pad, const float* sc, void* y, int64_t ldy,
+                    const mg_epilogue* e, hipStream_t st) {
+#define CONV_(...) return run_conv<T, TO, __VA_ARGS__>(x, B, H, W, Cin, wpack, Cout, KH, KW, stride, pad, sc, y, ldy, e, st)
+  if (sc || small_c) {  // modulation scale on load / per-lane tap decode
+    if constexpr (sizeof(T) == 2) {
+      if (BM == 128 && BN == 128) CONV_(128, 128, true, true);
+      if (BN == 256) CONV_(128, 256, true, true);
+    }
+    if (sc) CONV_(64, 64, true, true);
+    CONV_(64, 64, false, true);
   }
-  const bool small_c = Cin < max_tile_bk<T>();  // a K step spans several taps: per-lane tap decode
-  if (small_c ? conv_slabs<T, TO, true>(x, B, H, W, Cin, wpack, Cout, KH, KW, stride, pad, sc, y, ldy, e, st)
-              : conv_slabs<T, TO, false>(x, B, H, W, Cin, wpack, Cout, KH, KW, stride, pad, sc, y, ldy, e, st))
-    return;
-  const int tile = g_mg_tune[MG_TUNE_CONV_TILE];
   if constexpr (sizeof(T) == 2) {
-    // modulation-scaled loads on 128^2 tiles when the grid still covers the chip (measured at B=256: the
-    // 16x16 modulated 3x3 conv, 128 -> 128 channels, 58 -> 47 us; the 8x8 one stays on 64^2)
-    if (sc && !small_c && (tile == 128 || (tile == 0 && cdiv(B * ((H + 2 * pad - KH) / stride + 1) *
-                                                                  ((W + 2 * pad - KW) / stride + 1), 128) *
-                                                             (int64_t)cdiv(Cout, 128) >= 480))) {
-      run_conv<T, TO, 128, 128, true, true>(x, B, H, W, Cin, wpack, Cout, KH, KW, stride, pad, sc, y, ldy, e, st);
-      return;
-    }
-    if (sc && !small_c && tile == 257) {
-      run_conv<T, TO, 128, 256, true, true>(x, B, H, W, Cin, wpack, Cout, KH, KW, stride, pad, sc, y, ldy, e, st);
-      return;
-    }
+    if (BN == 32) CONV_(128, 32);
+    if (BN == 256) CONV_(128, 256);
+    if (BM == 256) CONV_(256, 128);
   }
-  if (sc || small_c) {  // modulation scale on load / small Cin: generic 64x64 instantiations
-    if (sc) run_conv<T, TO, 64, 64, true, true>(x, B, H, W, Cin, wpack, Cout, KH, KW, stride, pad, sc, y, ldy, e, st);
-    else run_conv<T, TO, 64, 64, false, true>(x, B, H, W, Cin, wpack, Cout, KH, KW, stride, pad, sc, y, ldy, e, st);
-    return;
-  }
-  int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
-  int64_t M = (int64_t)B * OH * OW;
-  if constexpr (sizeof(T) == 2) {
-    // 8-fragment wave tiles (128 x 64 / 64 x 128 per wave): 25 % fewer LDS bytes per MFMA.  128 x 256 by
-    // default when Cout fills it and the grid still covers the chip (measured at B=256: the
-    // discriminator's 4x4/s2 conv, N = 256, 100 -> 92 us; one column tile also reads the input once)
-    // narrow outputs (the MTM offset heads, Cout = 32) over many pixels: 128 x 32 tiles, no MFMA columns wasted
-    if (tile == 0 && Cout <= 32 && M >= 32768) {
-      run_conv<T, TO, 128, 32>(x, B, H, W, Cin, wpack, Cout, KH, KW, stride, pad, sc, y, ldy, e, st);
-      return;
-    }
-    if (tile == 257 || (tile == 0 && Cout % 256 == 0 && cdiv(M, 128) * (int64_t)(Cout / 256) >= 480 &&
-                        !(KH * KW * Cin <= 256 && M >= 16384))) {
-      run_conv<T, TO, 128, 256>(x, B, H, W, Cin, wpack, Cout, KH, KW, stride, pad, sc, y, ldy, e, st);
-      return;
-    }
-    if (tile == 256) {
-      run_conv<T, TO, 256, 128>(x, B, H, W, Cin, wpack, Cout, KH, KW, stride, pad, sc, y, ldy, e, st);
-      return;
-    }
-  }
-  // 1x1 convs over many pixels (K = Cin <= 256): latency-bound single-step tiles, as the short-K GEMMs above
-  const bool short_k = KH * KW * Cin <= 256 && M >= 16384;
-  if (tile == 128 || (tile == 0 && !short_k && cdiv(M, 128) * (int64_t)cdiv(Cout, 128) >= 480 && Cout > 64))
-    run_conv<T, TO, 128, 128>(x, B, H, W, Cin, wpack, Cout, KH, KW, stride, pad, sc, y, ldy, e, st);
-  else
-    run_conv<T, TO, 64, 64>(x, B, H, W, Cin, wpack, Cout, KH, KW, stride, pad, sc, y, ldy, e, st);
+  if (BM == 128) CONV_(128, 128);
+  CONV_(64, 64);
+#undef CONV_
 }
 }  // namespace
 
@@ -590,13 +460,22 @@ extern "C" int mg_conv2d_fwd(int dtype, const void* x, int B, int H, int W, int 
     MG_REQUIRE(KH == 3 && KW == 3 && stride == 1 && pad == 1 && !in_scale, "mg_epilogue.gs: 3x3 / stride 1 / pad 1, no in_scale");
     return mg_modgrad_conv(dtype, x, B, H, W, Cin, wpack, Cout, y, ldy, y_dtype, ep, st);
   }
-  if (dtype == MG_F32) {
-    if (y_dtype == MG_F32) run_conv_tiles<float, float>(x, B, H, W, Cin, wpack, Cout, KH, KW, stride, pad, in_scale, y, ldy, ep, st);
-    else run_conv_tiles<float, bf16_t>(x, B, H, W, Cin, wpack, Cout, KH, KW, stride, pad, in_scale, y, ldy, ep, st);
-  } else {
-    if (y_dtype == MG_F32) run_conv_tiles<bf16_t, float>(x, B, H, W, Cin, wpack, Cout, KH, KW, stride, pad, in_scale, y, ldy, ep, st);
-    else run_conv_tiles<bf16_t, bf16_t>(x, B, H, W, Cin, wpack, Cout, KH, KW, stride, pad, in_scale, y, ldy, ep, st);
+  const bool bf16 = dtype == MG_BF16, atomic = ep && ep->atomic;
+  Plan p = plan_conv_fwd(bf16, B, H, W, Cin, Cout, KH, KW, stride, pad, in_scale != nullptr, atomic);
+  if (p.route == ROUTE_DIRECT) {
+    if (mg_conv3_direct(x, B, H, Cin, wpack, Cout, ep, y, ldy, y_dtype, st)) return mg_check_launch("mg_conv2d_fwd");
+    p = plan_conv_fwd(bf16, B, H, W, Cin, Cout, KH, KW, stride, pad, false, atomic, true);
   }
+  with_types(false, dtype, y_dtype, [&](auto t, auto to, auto) {
+    using T = decltype(t);
+    using TO = decltype(to);
+    if (p.route == ROUTE_SLABS &&
+        (p.small_c ? conv_slabs<T, TO, true>(p, x, B, H, W, Cin, wpack, Cout, KH, KW, stride, pad, y, ldy, ep, st)
+                   : conv_slabs<T, TO, false>(p, x, B, H, W, Cin, wpack, Cout, KH, KW, stride, pad, y, ldy, ep, st)))
+      return;
+    run_conv_tiles<T, TO>(p.fb_BM, p.fb_BN, p.small_c, x, B, H, W, Cin, wpack, Cout, KH, KW, stride, pad, in_scale, y,
+                          ldy, ep, st);
+  });
   return mg_check_launch("mg_conv2d_fwd");
 }
 
@@ -622,11 +501,6 @@ void run_wgrad(const void* gy, int64_t ldg, const void* x, int B, int H, int W, 
 
 // Weight gradient with split-K into fp32 slabs written by the 8-column vector epilogue (coalesced, no atomics),
 // then the slab fold into the reference layout (mg_fold.hip: immediate, or deferred to the backward's flush).  Returns false when the workspace cannot be had (caller falls back to atomics).
-// stride-1 "same" convolution whose weight gradient can use the cheap-address column loader (LdMCConvS1)
-inline bool wgrad_s1(int H, int W, int KH, int KW, int stride, int pad, int tbk) {
-  return stride == 1 && KH == KW && 2 * pad == KH - 1 && W <= tbk && H <= 32 && pow2(H) && pow2(W);
-}
-
 template <typename T, int BM, int BN, bool XF = false, bool BG = false>
 bool run_wgrad_slabs(const void* gy, int64_t ldg, const void* x, int B, int H, int W, int Cin, const float* sc,
                      int Cout, int KH, int KW, int stride, int pad, float* gw, int splits, hipStream_t st,
@@ -1073,12 +947,11 @@ extern "C" int mg_conv2d_dgrad_s2(int dtype, const void* g, int B, int OH, int O
   MG_REQUIRE(!(ep && ep->atomic) || out_dtype == MG_F32, "atomic epilogue requires fp32 output");
   if (B == 0) return MG_OK;
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-  if (dtype == MG_F32) {
-    if (out_dtype == MG_F32) (Cg < max_tile_bk<float>() ? run_dgrad_s2<float, float, true>(g, B, OH, OW, Cg, wcls, Cin, out, ldo, ep, st) : run_dgrad_s2<float, float, false>(g, B, OH, OW, Cg, wcls, Cin, out, ldo, ep, st));
-    else (Cg < max_tile_bk<float>() ? run_dgrad_s2<float, bf16_t, true>(g, B, OH, OW, Cg, wcls, Cin, out, ldo, ep, st) : run_dgrad_s2<float, bf16_t, false>(g, B, OH, OW, Cg, wcls, Cin, out, ldo, ep, st));
-  } else {
-    if (out_dtype == MG_F32) (Cg < max_tile_bk<bf16_t>() ? run_dgrad_s2<bf16_t, float, true>(g, B, OH, OW, Cg, wcls, Cin, out, ldo, ep, st) : run_dgrad_s2<bf16_t, float, false>(g, B, OH, OW, Cg, wcls, Cin, out, ldo, ep, st));
-    else (Cg < max_tile_bk<bf16_t>() ? run_dgrad_s2<bf16_t, bf16_t, true>(g, B, OH, OW, Cg, wcls, Cin, out, ldo, ep, st) : run_dgrad_s2<bf16_t, bf16_t, false>(g, B, OH, OW, Cg, wcls, Cin, out, ldo, ep, st));
-  }
+  with_types(false, dtype, out_dtype, [&](auto t, auto to, auto) {
+    using T = decltype(t);
+    using TO = decltype(to);
+    if (Cg < max_tile_bk<T>()) run_dgrad_s2<T, TO, true>(g, B, OH, OW, Cg, wcls, Cin, out, ldo, ep, st);
+    else run_dgrad_s2<T, TO, false>(g, B, OH, OW, Cg, wcls, Cin, out, ldo, ep, st);
+  });
   return mg_check_launch("mg_conv2d_dgrad_s2");
 }

@@ -41,6 +41,15 @@ Epi<TO> make_epi(void* C, int64_t ldc, const mg_epilogue* e) {
   return ep;
 }
 
+// (x3, dtype, c_dtype) -> f(T{}, TO{}, std::bool_constant<X3>{}): operand storage type, output type, and whether
+// fp32 operands are multiplied as split bf16 (MG_F32X3: fp32 storage)
+template <class F>
+auto with_types(bool x3, int dtype, int c_dtype, F&& f) {
+  if (x3) return c_dtype == MG_F32 ? f(float{}, float{}, std::true_type{}) : f(float{}, bf16_t{}, std::true_type{});
+  if (dtype == MG_F32) return c_dtype == MG_F32 ? f(float{}, float{}, std::false_type{}) : f(float{}, bf16_t{}, std::false_type{});
+  return c_dtype == MG_F32 ? f(bf16_t{}, float{}, std::false_type{}) : f(bf16_t{}, bf16_t{}, std::false_type{});
+}
+
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 // Operands are fetched through buffer descriptors with 32-bit byte offsets (mg_gemm.h): every operand's
 // byte extent must stay below 2 GiB, or loads past it would silently return zeros.
@@ -52,7 +61,6 @@ inline int ilog2(int v) {
   while ((1 << l) < v) ++l;
   return l;
 }
-inline bool pow2(int v) { return v > 0 && (v & (v - 1)) == 0; }
 inline int kwinv(int KW) { return 65536 / KW + 1; }  // exact tap / KW for tap < 64
 
 }  // namespace mg

@@ -7,10 +7,10 @@
 //
 // Covered: the 1x1 data gradient (gyt [M, K] x W [K, N], mg_gemm with a_kc = 1, b_kc = 0) and the 3x3 / stride 1 /
 // pad 1 one through the flipped pack (mg_conv2d_fwd), operands bf16 with a bf16 or fp32 gx, or fp32 with an fp32 gx,
-// on the tile shapes the unfused dispatch picks for them (64^2, 128^2, 128 x 256).  Not covered, so left to the two
-// kernels: deterministic mode and tuning slot MG_TUNE_MODGRAD_UNFUSED; shapes the unfused call runs as split-K slabs
-// or through the direct 32-channel conv; HW < 16 or not a power of two; Cin % 8; gyt channels below one K step;
-// unaligned operands; the MX-fp8 data gradient (another entry point).
+// on the tile the plain call's plan names (mg_plan.h: asked, never re-derived here), where that is 64^2, 128^2 or
+// 128 x 256.  Not covered, so left to the two kernels: deterministic mode and tuning slot MG_TUNE_MODGRAD_UNFUSED;
+// plans that are split-K slabs, the direct 32-channel conv or another tile; HW < 16 or not a power of two; Cin % 8;
+// gyt channels below one K step; unaligned operands; the MX-fp8 data gradient (another entry point).
 #include "mg_gemm.h"
 #include "mg_host.h"
 
@@ -22,36 +22,10 @@ constexpr Grouping kNoGroup{0, 1, nullptr, nullptr, 0};
 
 inline bool unfused_mode() { return mg_det() || g_mg_tune[MG_TUNE_MODGRAD_UNFUSED] != 0; }
 
-// the output tile of the unfused mg_gemm call (run_plain_tiles) at splits = 1: 64, 128, or 257 = 128 x 256; tuning
-// slot MG_TUNE_GEMM_TILE forces one as it does there
-inline int gemm_tile_pick(bool bf16, int M, int N, int K) {
-  const int tile = g_mg_tune[MG_TUNE_GEMM_TILE];
-  if (tile == 0 && (K <= (bf16 ? Tile<bf16_t>::BK : Tile<float>::BK) || (K <= 256 && M >= 16384))) return 64;
-  if (bf16 && (tile == 257 || (tile == 0 && N % 256 == 0 && (int64_t)cdiv(M, 128) * (N / 256) >= 480))) return 257;
-  return (tile == 128 || (tile == 0 && (int64_t)cdiv(M, 128) * cdiv(N, 128) >= 480)) ? 128 : 64;
-}
-// would the unfused mg_gemm call run as split-K slabs (run_splitk_slabs)
-inline bool gemm_slabs(bool bf16, int M, int N, int K) {
-  if (g_mg_tune[MG_TUNE_NO_SLABS]) return false;
-  const int tbk = bf16 ? tile_bk<bf16_t, false, 64, 64>() : tile_bk<float, false, 64, 64>();
-  const int64_t tiles = (int64_t)cdiv(M, 64) * cdiv(N, 64);
-  if (tiles >= 96 || K < 4 * tbk) return false;
-  return std::min<int64_t>(256 / tiles, K / (2 * tbk)) >= 2;
-}
-// the same two questions for the unfused mg_conv2d_fwd call (run_conv_tiles / conv_slabs_t), 3x3 / s1 / p1, Cin >= BK
-inline int conv_tile_pick(bool bf16, int M, int Cout) {  // (MG_TUNE_CONV_TILE forces a tile; 256 x 128 is not built fused)
-  const int tile = g_mg_tune[MG_TUNE_CONV_TILE];
-  if (bf16 && (tile == 257 || (tile == 0 && Cout % 256 == 0 && cdiv(M, 128) * (int64_t)(Cout / 256) >= 480))) return 257;
-  return (tile == 128 || (tile == 0 && cdiv(M, 128) * (int64_t)cdiv(Cout, 128) >= 480 && Cout > 64)) ? 128 : 64;
-}
-inline bool conv_slabs(bool bf16, int M, int Cout, int K) {
-  if (g_mg_tune[MG_TUNE_NO_SLABS]) return false;
-  const bool narrow = bf16 && Cout <= 32;
-  const int tbk = bf16 ? tile_bk<bf16_t, false, 64, 64>() : tile_bk<float, false, 64, 64>();
-  const int64_t tiles = (int64_t)cdiv(M, narrow ? 128 : 64) * cdiv(Cout, narrow ? 32 : 64);
-  const int ksteps = K / tbk;
-  if (tiles >= 1024 || ksteps < 16) return false;
-  return std::min<int64_t>(cdiv(1024, tiles), ksteps / 8) >= 2;
+// the plain call's plan: mg_gemm(gyt [M, Cg] x W [Cg, Cin]) for k = 1, mg_conv2d_fwd (3x3 / s1 / p1) for k = 3
+inline Plan plain_plan(bool bf16, int k, int B, int H, int W, int Cg, int Cin) {
+  return k == 1 ? plan_gemm(bf16, false, B * H * W, Cin, Cg, GemmEpi{false, false, false}, 1)
+                : plan_conv_fwd(bf16, B, H, W, Cg, Cin, 3, 3, 1, 1, false, false);
 }
 
 // why a call is not covered (nullptr: covered).  k: 1 or 3; Cg = channels of gyt (the reduction is k * k * Cg),
@@ -68,16 +42,16 @@ const char* refuse(int dtype, int gx_dtype, int k, int B, int H, int W, int Cg, 
   if (Cin % 8 || Cg % 8) return "channels must be multiples of 8";
   if (!s || !x || !gx || !aligned16(s) || !aligned16(x) || !aligned16(gx) || ld_s % 4 || ld_x % 8 || ld_gx % 8)
     return "s / x / gx must be 16-byte aligned with pitches that keep rows so";
-  if (k == 1) {
-    if (gemm_slabs(bf16, (int)M, Cin, Cg)) return "the unfused GEMM runs as split-K slabs";
-  } else {
+  if (k == 3) {
     if (!pow2(H) || !pow2(W) || !pow2(Cg)) return "3x3: H, W and the gradient's channels must be powers of two";
-    if (Cg < (bf16 ? max_tile_bk<bf16_t>() : max_tile_bk<float>())) return "3x3: gradient channels below one K step";
-    if (bf16 && mg_conv3_direct_ok(H, W, Cg, Cin, 3, 3, 1, 1, false)) return "the unfused conv runs direct";
-    if (conv_slabs(bf16, (int)M, Cin, 9 * Cg)) return "the unfused conv runs as split-K slabs";
-    if (bf16 && Cin <= 32 && M >= 32768 && g_mg_tune[MG_TUNE_CONV_TILE] == 0) return "the unfused conv runs on 128 x 32 tiles";
-    if (g_mg_tune[MG_TUNE_CONV_TILE] == 256) return "256 x 128 tiles are not built fused";
+    if (Cg < max_tile_bk_of(bf16)) return "3x3: gradient channels below one K step";
   }
+  const Plan p = plain_plan(bf16, k, B, H, W, Cg, Cin);
+  if (p.route == ROUTE_DIRECT) return "the unfused conv runs direct";
+  if (p.route == ROUTE_SLABS) return k == 1 ? "the unfused GEMM runs as split-K slabs" : "the unfused conv runs as split-K slabs";
+  if (p.BN == 32) return "the unfused conv runs on 128 x 32 tiles";
+  // (fp32 has no 256 x 128 tile, so its plan ignores the slot; the fused form has always declined under it)
+  if (p.BM == 256 || (k == 3 && g_mg_tune[MG_TUNE_CONV_TILE] == 256)) return "256 x 128 tiles are not built fused";
   return nullptr;
 }
 
@@ -126,6 +100,23 @@ bool run_conv(const void* x, int B, int H, int W, int Cin, const void* wpack, in
   return true;
 }
 
+// f(T{}, TO{}, BM, BN) on the plan's tile, for the (operand, gx) types and tiles built fused (refuse() admits no other)
+template <class F>
+bool on_plan_tile(int dtype, int gx_dtype, const Plan& p, F&& f) {
+  return with_types(false, dtype, gx_dtype, [&](auto t, auto to, auto) {
+    using I64 = std::integral_constant<int, 64>;
+    using I128 = std::integral_constant<int, 128>;
+    if constexpr (sizeof(t) == 4 && sizeof(to) == 2) return false;
+    else {
+      if (p.BM == 64) return f(t, to, I64{}, I64{});
+      if constexpr (sizeof(t) == 2) {
+        if (p.BN == 256) return f(t, to, I128{}, std::integral_constant<int, 256>{});
+      }
+      return f(t, to, I128{}, I128{});
+    }
+  });
+}
+
 }  // namespace
 
 extern "C" int mg_modconv_dgrad_fusable(int dtype, int gx_dtype, int k, int B, int H, int W, int Cout, int Cin,
@@ -149,17 +140,10 @@ int mg_modgrad_gemm(int dtype, int M, int N, int K, const void* A, int64_t lda, 
   MG_REQUIRE(e->scale_shift >= 0 && e->scale_shift < 31 && M % HW == 0, "M must be whole images of 1 << scale_shift pixels");
   // (H, W only matter to the 3x3 form)
   MG_MODGRAD_REQUIRE(refuse(dtype, c_dtype, 1, M / HW, HW, 1, K, N, e->scale, e->scale_ld, e->gs_x, e->ld_gs_x, C, ldc));
-  const bool bf16 = dtype == MG_BF16;
-  const int tile = gemm_tile_pick(bf16, M, N, K);
-  bool ok;
-#define RUN_(T, TO)                                                                                   \
-  (tile == 257 ? run_gemm<T, TO, 128, (sizeof(T) == 2 ? 256 : 128)>(M, N, K, A, lda, B, ldb, C, ldc, e, st) \
-   : tile == 128 ? run_gemm<T, TO, 128, 128>(M, N, K, A, lda, B, ldb, C, ldc, e, st)                  \
-                 : run_gemm<T, TO, 64, 64>(M, N, K, A, lda, B, ldb, C, ldc, e, st))
-  if (!bf16) ok = RUN_(float, float);
-  else if (c_dtype == MG_F32) ok = RUN_(bf16_t, float);
-  else ok = RUN_(bf16_t, bf16_t);
-#undef RUN_
+  const Plan p = plain_plan(dtype == MG_BF16, 1, M / HW, HW, 1, K, N);
+  const bool ok = on_plan_tile(dtype, c_dtype, p, [&](auto t, auto to, auto bm, auto bn) {
+    return run_gemm<decltype(t), decltype(to), decltype(bm)::value, decltype(bn)::value>(M, N, K, A, lda, B, ldb, C, ldc, e, st);
+  });
   MG_REQUIRE(ok, "operands not aligned for the vector epilogue");
   return mg_check_launch("mg_gemm (modulated-conv data gradient, gx / gs in the epilogue)");
 }
@@ -169,17 +153,10 @@ int mg_modgrad_conv(int dtype, const void* x, int B, int H, int W, int Cin, cons
   MG_MODGRAD_REQUIRE(refuse_epi(e));
   MG_REQUIRE(e->scale_shift == ilog2(H * W) && pow2(H * W), "scale_shift must be log2(H * W)");
   MG_MODGRAD_REQUIRE(refuse(dtype, y_dtype, 3, B, H, W, Cin, Cout, e->scale, e->scale_ld, e->gs_x, e->ld_gs_x, y, ldy));
-  const bool bf16 = dtype == MG_BF16;
-  const int tile = conv_tile_pick(bf16, B * H * W, Cout);
-  bool ok;
-#define RUN_(T, TO)                                                                                      \
-  (tile == 257 ? run_conv<T, TO, 128, (sizeof(T) == 2 ? 256 : 128)>(x, B, H, W, Cin, wpack, Cout, y, ldy, e, st) \
-   : tile == 128 ? run_conv<T, TO, 128, 128>(x, B, H, W, Cin, wpack, Cout, y, ldy, e, st)                 \
-                 : run_conv<T, TO, 64, 64>(x, B, H, W, Cin, wpack, Cout, y, ldy, e, st))
-  if (!bf16) ok = RUN_(float, float);
-  else if (y_dtype == MG_F32) ok = RUN_(bf16_t, float);
-  else ok = RUN_(bf16_t, bf16_t);
-#undef RUN_
+  const Plan p = plain_plan(dtype == MG_BF16, 3, B, H, W, Cin, Cout);
+  const bool ok = on_plan_tile(dtype, y_dtype, p, [&](auto t, auto to, auto bm, auto bn) {
+    return run_conv<decltype(t), decltype(to), decltype(bm)::value, decltype(bn)::value>(x, B, H, W, Cin, wpack, Cout, y, ldy, e, st);
+  });
   MG_REQUIRE(ok, "operands not aligned for the vector epilogue");
   return mg_check_launch("mg_conv2d_fwd (modulated-conv data gradient, gx / gs in the epilogue)");
 }

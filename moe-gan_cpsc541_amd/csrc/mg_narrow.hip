@@ -351,17 +351,6 @@ bool conv_dispatch(const void* x, int B, int S, int Cin, const void* wpack, int 
 
 }  // namespace
 
-bool mg_conv3_direct_ok(int H, int W, int Cin, int Cout, int KH, int KW, int stride, int pad, bool wgrad) {
-  // A/B: 1 every form through the implicit GEMM; 2 / 3 / 4 only the forward / data-gradient / weight-gradient form
-  const int off = g_mg_tune[MG_TUNE_NARROW];
-  if (off == 1 || (wgrad && off == 4) || (!wgrad && off == (Cin == 32 ? 3 : 2))) return false;
-  if (KH != 3 || KW != 3 || stride != 1 || pad != 1 || H != W || (H != 4 && H != 8 && H != 16)) return false;
-  // the data-gradient form over 16x16 maps into >= 256 channels is output-bound (a read-modify-write of the whole
-  // gradient) and the implicit GEMM streams that faster (31 vs 34 us at B=256, profiles/round4_narrow_probe.txt)
-  if (Cin == 32 && H >= 16 && Cout >= 256) return false;
-  return (Cout == 32 && Cin % 64 == 0) || (Cin == 32 && Cout % 64 == 0);
-}
-
 bool mg_conv3_direct(const void* x, int B, int H, int Cin, const void* wpack, int Cout, const mg_epilogue* e, void* y,
                      int64_t ldy, int y_dtype, hipStream_t st) {
   if (e && (e->atomic || e->remap_taps > 0 || e->a_idx || e->a_rowscale || e->a_gelu)) return false;

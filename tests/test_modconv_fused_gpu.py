@@ -241,6 +241,25 @@ def test_fused_large_tiles_against_fp64(no_slabs, cdt, k, tile):
         L.call("mg_set_tuning", slot, 0)
 
 
+@pytest.mark.parametrize("Cin", [1024, 2048], ids=["128x128", "128x256"])
+@pytest.mark.parametrize("k", [1, 3])
+def test_fused_default_large_tiles(k, Cin):
+    """Default tuning, no slot set, at the smallest shapes where the dispatch's own rule leaves 64^2 tiles: bf16
+    operands and gx, B = 32 at 16 x 16 (M = 8192 rows, 64 row tiles of 128), 512 gradient channels for the 1x1 and 64
+    for the 3x3, into Cin = 1024 (512 tiles of 128^2, from 480 on) and Cin = 2048 (512 tiles of 128 x 256).  The
+    fused entry point launches on the tile the plain call's plan names (csrc/mg_plan.h); tests/test_plan_cpu.py pins
+    these four plans to one launch on 128^2 / 128 x 256, which a GPU test cannot see.  Here: the library admits the
+    call, gx has the bits of the explicit two-kernel sequence, and gs is within the two-run bound of
+    check_same_as_two_kernels (mg_modconv_bwd_in splits an image over grid.z at HW = 256: n = 2 (HW + 3))."""
+    B, H, W = 32, 16, 16
+    c = Case(BF16, BF16, k, B, H, W, Cin, 512 if k == 1 else 64, 0, seed=11000 + 10 * k + Cin)
+    gx, _, _ = c.outputs()
+    assert ops.modconv_dgrad_fusable(c.gyt_d, k, B, H, W, Cin, c.x_d, c.Sd[:, c.sl], gx), c.tag() + ": not admitted"
+    fused, gx, buf, Gd = c.run()
+    assert fused, c.tag() + ": did not run fused"
+    c.check_same_as_two_kernels(gx, buf, Gd, exact_gs=False)
+
+
 @pytest.mark.parametrize("mode", ["deterministic", "slot29"])
 @pytest.mark.parametrize("k", [1, 3])
 @pytest.mark.parametrize("cdt", [BF16, F32], ids=["bf16", "f32"])
