@@ -273,6 +273,25 @@ int mg_clip_patches_bwd(int g_dtype, const void* g_patches, int img_dtype, const
    g_f = -(scale[0] / B) (t^ - cos f^) / |f| (zero rows where the similarity is not finite); scale is a device scalar. */
 int mg_cos_loss(const float* f, const float* text, int B, int C, const float* scale, float* loss, float* g_f, void* stream);
 
+/* Contrastive CLIP loss, image -> text, over fp32 image features f [B, C] (row stride ldf) and caption features
+   t [N, C] (row stride ldt, N >= B, constants: no gradient), C = 64 or 512, 1 <= B <= N <= 2^20; row i's positive
+   is column pos_off + i (0 <= pos_off, pos_off + B <= N); tau > 0 is the temperature, scale a device scalar.
+   With f^ = f / |f|, t^ = t / |t|, s_ij = <f^_i, t^_j> / tau: column j is live iff |t_j| is finite and non-zero,
+   row i is live iff |f_i| is finite and non-zero and its positive column is live, p_ij = softmax of s_i. over the
+   live j, and
+     loss[0] = (1 / B) sum_{live i} [ logsumexp_{live j} s_ij - s_{i, pos_off + i} ]        (a dead row adds 0)
+     g_f[i]  = scale[0] / (B tau) (I - f^_i f^_i^T) / |f_i| (sum_{live j} p_ij t^_j - t^_{pos_off + i})
+   (g_f fp32 [B, C] contiguous; a dead row's gradient row is zeros).  Flash-style: 64 x 64 tiles of exact-fp32 MFMA
+   dots (the chain of mg_poly_mmd_sums), the row maximum subtracted, every reduction fp64 in a fixed order, a block
+   owning 64 rows and one of S(B, N) column segments (S as for mg_knn_radius2 below): no B x N buffer, no atomics,
+   bitwise repeatable; launch counts and grids depend on (B, N, C) alone.  `work` is caller-owned device memory of
+     nwork >= 3 B + N + 2 B S + (S > 1 ? B C S : 0)   doubles
+   (inverse norms, positive logits, row logsumexps, per-segment (max, sum) pairs and per-segment gradient strips);
+   no other memory is used.  Nothing is written when an argument is refused. */
+int mg_clip_contrast(const float* f, int64_t ldf, int B, const float* t, int64_t ldt, int N, int C, int pos_off,
+                     float tau, const float* scale, double* work, int64_t nwork, float* loss, float* g_f,
+                     void* stream);
+
 /* LayerNorm over C (128/256/512/768) per row (+ optional LeakyReLU), saving mean/rstd. t2i_moe_gan.py:505-507, :684. */
 int mg_layernorm_fwd(int dtype, const void* x, int64_t ldx, int R, int C, const float* gamma, const float* beta, float eps, void* y, int64_t ldy, float* mean, float* rstd, int act, void* stream);
 

@@ -7,64 +7,11 @@
 // per product) are exact enough; and the sums of an n x m kernel matrix are reduced tile by tile in fp64 so that
 // no n x m buffer exists and the result is bitwise repeatable (per-block partials, folded in a fixed order).
 //
-// Operand maps of the 32x32x2 f32 MFMA: lane l gives A[i = l & 31][k = l >> 5] and B[k = l >> 5][j = l & 31], one
-// VGPR each; D[i][j] sits at lane (j, h), register reg with i = (reg & 3) + 8 (reg >> 2) + 4 h.  Here B = (rows)^T,
-// so both operands are "row l & 31 of a staged tile, k chosen by l >> 5".  Inside a staged chunk of 32 k lane half
-// h reads the four k of one 16-B vector per step, so the chain visits k0 + 8 c + j, k0 + 8 c + 4 + j (c, then j):
-// a fixed permutation of k, the same for every output element.
-#include "mg_common.h"
+// The staging (Stage), the MFMA chain (mma_chunk, tile_dots) and the operand maps of the 32x32x2 f32 MFMA live in
+// mg_tile_f32.h, shared with the contrastive CLIP loss (mg_contrast.hip).
+#include "mg_tile_f32.h"
 
 namespace {
-
-typedef float f32x16_t __attribute__((ext_vector_type(16)));
-constexpr int kKC = 32;        // k per staged chunk
-constexpr int kLDP = kKC + 4;  // LDS row pitch (floats): rows stay 16-B aligned
-constexpr int kTile = 64;      // mg_poly_mmd_sums tile edge (the header documents it: the caller sizes partials)
-constexpr int kMaxRows = 1 << 20;
-
-// ROWS x kKC floats of P (rows [row0, row0 + ROWS), columns [k0, k0 + kKC)) through registers into LDS; rows at or
-// past row_end and columns at or past d are zeros and are never read from memory.
-template <int ROWS>
-struct Stage {
-  static constexpr int NV = ROWS * (kKC / 4) / 256;
-  f32x4_t v[NV];
-  MG_DEV void load(const float* __restrict__ P, int64_t ld, int64_t row0, int64_t row_end, int k0, int d) {
-#pragma unroll
-    for (int p = 0; p < NV; ++p) {
-      const int idx = threadIdx.x + p * 256;
-      const int64_t gr = row0 + (idx >> 3);
-      const int k = k0 + 4 * (idx & 7);
-      v[p] = (gr < row_end && k < d) ? *reinterpret_cast<const f32x4_t*>(P + gr * ld + k)
-                                     : f32x4_t{0.f, 0.f, 0.f, 0.f};
-    }
-  }
-  MG_DEV void store(float (*S)[kLDP]) const {
-#pragma unroll
-    for (int p = 0; p < NV; ++p) {
-      const int idx = threadIdx.x + p * 256;
-      *reinterpret_cast<f32x4_t*>(&S[idx >> 3][4 * (idx & 7)]) = v[p];
-    }
-  }
-};
-
-// acc[i][j] += sum over the staged chunk of A[ar + i][k] * B[br + j][k] (ar / br: this lane's row of each tile)
-MG_DEV void mma_chunk(const float (*A)[kLDP], const float (*B)[kLDP], int ar, int br, int h, f32x16_t& acc) {
-#pragma unroll
-  for (int c = 0; c < kKC / 8; ++c) {
-    const f32x4_t a = *reinterpret_cast<const f32x4_t*>(&A[ar][8 * c + 4 * h]);
-    const f32x4_t b = *reinterpret_cast<const f32x4_t*>(&B[br][8 * c + 4 * h]);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[j], b[j], acc, 0, 0, 0);
-  }
-}
-
-MG_DEV int acc_row(int reg, int h) { return (reg & 3) + 8 * (reg >> 2) + 4 * h; }
-
-MG_DEV double wave_sum_f64(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-  return v;
-}
 
 // Block t of the grid is one 64 x 64 tile: first the upper-triangle tiles of X X^T, then those of Y Y^T, then all
 // tiles of X Y^T.  Four waves, each a 32 x 32 quadrant.  part[t] = the tile's sum (off-diagonal tiles of the
@@ -229,35 +176,8 @@ __global__ __launch_bounds__(256) void k_retrieval_rank(const float* __restrict_
 
 constexpr int kDP = kTile + 1;     // pitch of the transposed dot tile (odd: the accumulator stores spread over banks)
 constexpr int kMaxK = 16;          // nearest_k <= 16
-constexpr int kMaxSplits = 8;      // column segments per launch <= 8
-constexpr int kSplitBlocks = 512;  // ... and no more than bring the grid to about this many blocks
-
-// column segments of a launch with `strips` row strips over `tiles` column tiles (the header documents it: the
-// caller sizes `work` by it)
-int col_splits(int strips, int tiles) { return std::max(1, std::min({tiles, kMaxSplits, cdiv(kSplitBlocks, strips)})); }
-
-// acc = this wave's 32 x 32 quadrant of A[arow0 ..] B[brow0 ..]^T over all of d, chunk by chunk as in
-// k_poly_mmd_tiles; every thread of the block calls it, and it ends on a barrier
-MG_DEV void tile_dots(const float* __restrict__ A, int64_t lda, int64_t arow0, int na, const float* __restrict__ B,
-                      int64_t ldb, int64_t brow0, int nb, int d, float (*As)[kLDP], float (*Bs)[kLDP], int ar, int br,
-                      int h, f32x16_t& acc) {
-#pragma unroll
-  for (int i = 0; i < 16; ++i) acc[i] = 0.f;
-  Stage<kTile> sa, sb;
-  sa.load(A, lda, arow0, na, 0, d);
-  sb.load(B, ldb, brow0, nb, 0, d);
-  for (int k0 = 0; k0 < d; k0 += kKC) {
-    sa.store(As);
-    sb.store(Bs);
-    __syncthreads();
-    if (k0 + kKC < d) {
-      sa.load(A, lda, arow0, na, k0 + kKC, d);
-      sb.load(B, ldb, brow0, nb, k0 + kKC, d);
-    }
-    mma_chunk(As, Bs, ar, br, h, acc);
-    __syncthreads();
-  }
-}
+// (col_splits, the column segments of a launch, and tile_dots, a wave's quadrant of one tile's dots, are in
+// mg_tile_f32.h)
 
 // The k smallest of the multiset get(0 .. N), ascending, to put(slot, value): round by round the smallest value
 // above the last one and how often it occurs (+inf fills what the multiset cannot: NaN entries are never taken).
@@ -602,9 +522,7 @@ __global__ __launch_bounds__(256) void k_moment_fold(const double* __restrict__ 
   }
 }
 
-bool rows_ok(const void* p, int64_t ld, int d) { return p && mg_al16(p) && ld >= d && (ld % 4) == 0; }
-bool dim_ok(int d) { return d >= 4 && d <= 1024 && (d % 4) == 0; }
-bool f64_ok(const void* p) { return p && ((uintptr_t)p & 7) == 0; }
+bool dim_ok(int d) { return d >= 4 && d <= 1024 && (d % 4) == 0; }  // (rows_ok, f64_ok: mg_tile_f32.h)
 
 }  // namespace
 

@@ -17,9 +17,9 @@ import json
 INT_KEYS = ("batch_size", "epochs", "kl_annealing_epochs", "lr_warmup_epochs", "eval_every", "eval_samples",
             "eval_nearest_k")
 FLOAT_KEYS = ("learning_rate", "beta1", "beta2", "r1_gamma", "clip_weight_16", "clip_weight_8", "kl_weight",
-              "balance_weight", "ema_kimg", "ema_rampup")
+              "balance_weight", "ema_kimg", "ema_rampup", "clip_temperature")
 # this build's switches: "true" / "1" / "yes" / "on" (any case) turn one on, "false" / "0" / "no" / "off" / "" off
-BOOL_KEYS = ("eval_frechet",)
+BOOL_KEYS = ("eval_frechet", "clip_contrastive")
 # this build's policy strings: "" / "none" / "off" / "false" / "0" (any case) mean off (None), anything else is kept
 # (stripped) for the training entry point to validate
 POLICY_KEYS = ("diffaug",)
@@ -53,6 +53,10 @@ TRAIN_KWARGS = {
     # this build's extension: differentiable augmentation of the discriminator's inputs, a comma-separated subset of
     # color,translation,cutout (moegan_mi/augment.py); off unless set
     "diffaug": ("diffaug", None),
+    # this build's extension: with clip_grad, the CLIP terms as a contrastive loss over the batch's captions at
+    # clip_temperature (0.07 = CLIP's initial temperature: a choice, not a measurement); off unless set
+    "clip_contrastive": ("clip_contrastive", False),
+    "clip_temperature": ("clip_temperature", 0.07),
 }
 # fixed by the SageMaker entry point (sagemaker_train.py:287-292)
 TRAIN_FIXED = {"log_interval": 100, "save_interval": 500, "gradient_accumulation_steps": 8,

@@ -1270,6 +1270,37 @@ def cos_loss(f, text, scale, loss=None, g_f=None):
     return loss, g_f
 
 
+def clip_contrast_work(B, N, C):
+    """Doubles mg_clip_contrast needs in its workspace (include/moegan_hip.h)."""
+    S = prdc_splits(B, N)
+    return 3 * B + N + 2 * B * S + (B * C * S if S > 1 else 0)
+
+
+def clip_contrast(f, t, tau, scale, pos_off=0, loss=None, g_f=None):
+    """Contrastive CLIP loss of image features f [B, C] against caption features t [N, C] (N >= B; row i's positive
+    is column pos_off + i): (1 / B) sum_i [logsumexp_j s_ij - s_{i, pos_off + i}] with s = <f^, t^> / tau, and
+    d loss / d f times the device scalar ``scale`` (mg_clip_contrast: exact-fp32 MFMA dots, fp64 fixed-order
+    reductions, no B x N buffer; dead rows / columns as include/moegan_hip.h).  fp32; the captions get no gradient.
+    The workspace comes from the step's arena.  Returns (loss [1], g_f [B, C])."""
+    f, t = _feature_rows(f, "f"), _feature_rows(t, "t")
+    B, C = f.shape
+    N = t.shape[0]
+    if t.shape[1] != C:
+        raise L.MGError(f"clip_contrast: f has {C} columns, t {t.shape[1]}")
+    if scale.dtype != torch.float32 or scale.numel() != 1:
+        raise L.MGError("clip_contrast: scale must be one fp32 device scalar")
+    loss = torch.empty(1, device=f.device) if loss is None else loss
+    g_f = torch.empty(B, C, device=f.device) if g_f is None else g_f
+    if g_f.dtype != torch.float32 or tuple(g_f.shape) != (B, C) or not g_f.is_contiguous():
+        raise L.MGError(f"clip_contrast: g_f must be contiguous fp32 [{B}, {C}]")
+    need = clip_contrast_work(max(B, 1), max(N, 1), C)
+    work = (zeros(need, device=f.device, dtype=torch.float64) if ARENA.active
+            else torch.empty(need, device=f.device, dtype=torch.float64))
+    call("mg_clip_contrast", ptr(f), f.stride(0), B, ptr(t), t.stride(0), N, C, int(pos_off), float(tau), ptr(scale),
+         ptr(work), work.numel(), ptr(loss), ptr(g_f), S())
+    return loss, g_f
+
+
 def g_loss(fake, out, g, scale=1.0):
     call("mg_g_loss", ptr(fake), fake.shape[0], scale, ptr(out), ptr(g), S())
 

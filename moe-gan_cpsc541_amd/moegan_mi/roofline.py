@@ -61,6 +61,9 @@ FAMILIES = {
     # scalar losses, guard words, optimizer prologue: a few hundred bytes each, launch-latency bound
     "losses_flags": ("hbm", ("mg_d_loss", "mg_g_loss", "mg_finite_flag", "mg_flag_window", "mg_kl_coefs", "mg_balance",
                              "mg_opt_prologue", "mg_guard_update", "mg_cos_loss")),
+    # contrastive CLIP loss (mg_contrast.hip): B x N logits recomputed tile by tile, never stored; at the step's batch
+    # sizes its five launches are latency-sized, so it is priced by the bytes it has to move
+    "clip_contrast": ("hbm", ("mg_clip_contrast",)),
 }
 _FAMILY_OF = {e: f for f, (_, es) in FAMILIES.items() for e in es}
 
@@ -100,6 +103,7 @@ KERNELS = [
     (r"k_d_loss|k_g_loss|k_finite_flag|k_flag_window|k_guard_update|k_kl_coefs|k_balance|k_opt_prologue|"
      r"k_cos_loss",
      "losses_flags"),
+    (r"k_contrast_norms|k_contrast_stats|k_contrast_fold|k_contrast_grad|k_contrast_apply", "clip_contrast"),
 ]
 
 
@@ -329,6 +333,15 @@ def work(name, a):
         return a["B"] * 8.0
     if name == "mg_cos_loss":  # features and text in, the feature gradient out
         return a["B"] * a["C"] * 12.0 + 8
+    if name == "mg_clip_contrast":
+        # features and captions read by the norms and by both tile passes (a strip's rows once per column segment,
+        # the segment's captions once per strip and again for the second chain), the gradient written once, the
+        # fp64 per-segment strips written and read once when there are several segments
+        B, N, C = a["B"], a["N"], a["C"]
+        strips, tiles = -(-B // 64), -(-N // 64)
+        S = max(1, min(tiles, 8, -(-512 // strips)))
+        rows = (B + N) + 2 * B * S + 3 * strips * N
+        return 4.0 * C * (rows + B) + (16.0 * B * C * S if S > 1 else 8.0 * B * C) + 8.0 * (4 * B + N + 4 * B * S)
     if name == "mg_finite_flag":
         return 4.0 * a["n"]
     if name == "mg_kl_coefs":

@@ -19,6 +19,9 @@ and its feature gradient in one launch (mg_cos_loss), and the tower's backward
 (clip_vit.ClipImageEncoder.backward) adds clip_weight_16 * d L_clip / d img16 to the adversarial image gradient and
 writes clip_weight_8 * d L_clip / d img8, which the generator backward takes as ``g_img8``: the half-resolution
 to_rgb then trains, so the store keeps it inside the optimised range (layout.frozen_rgb_prefixes(clip_grad=True)).
+``StepConfig(clip_grad=True, clip_loss="contrastive")`` swaps the term alone: a softmax over the global batch's
+captions with the image's own caption as the positive (mg_clip_contrast; under data parallelism the captions are
+gathered once per step, the features are not); the tower passes, the weights, the guard and the logged keys stay.
 
 Loss guards (t2i_moe_gan.py:1315-1320, :1367-1376, :1396-1404) run on the device: a flag word per step
 (``out["flags"]``) records a non-finite discriminator loss (the whole batch is skipped: no gradient is
@@ -53,7 +56,11 @@ class StepConfig:
     def __init__(self, E=4, topk=None, dtype="fp32", r1_gamma=10.0, clip_weight_16=0.1, clip_weight_8=0.05,
                  balance_weight=0.01, beta1=0.5, beta2=0.999, weight_decay=0.01, eps=1e-8, d_clip=0.7, g_clip=0.8,
                  psi=0.7, fp8=False, max_res=16, deterministic=None, clip_grad=False, ema_halflife=None,
-                 ema_rampup=None, diffaug=None):
+                 ema_rampup=None, diffaug=None, clip_loss="cosine", clip_temperature=0.07):
+        """``clip_loss`` (with ``clip_grad=True``): "cosine" = the reference's 1 - mean cos(image, own caption);
+        "contrastive" = a softmax over the (global) batch's captions with the image's own caption as the positive
+        (ops.clip_contrast), at temperature ``clip_temperature``.  The default 0.07 is CLIP's initial temperature: a
+        choice, not a measurement -- it is explicit because the weight loaders drop the checkpoint's logit_scale."""
         self.E, self.topk = E, topk
         # differentiable augmentation of the discriminator's inputs (this build's extension, moegan_mi/augment.py): a
         # policy string, any comma-separated subset of color,translation,cutout; None = off (the reference's step)
@@ -73,6 +80,13 @@ class StepConfig:
         # the CLIP terms train the generator (needs the build's image tower as TrainStep's clip_encoder); False: the
         # reference's gradient-free terms
         self.clip_grad = bool(clip_grad)
+        if clip_loss not in ("cosine", "contrastive"):
+            raise ValueError(f"clip_loss must be 'cosine' or 'contrastive', got {clip_loss!r}")
+        if clip_loss == "contrastive" and not self.clip_grad:
+            raise ValueError("clip_loss='contrastive' needs clip_grad=True (the gradient-free terms stay the cosine)")
+        if not float(clip_temperature) > 0 or float(clip_temperature) == float("inf"):
+            raise ValueError(f"clip_temperature must be positive and finite, got {clip_temperature}")
+        self.clip_loss, self.clip_temperature = clip_loss, float(clip_temperature)
         # exponential moving average of the generator (this build's extension): half-life in optimizer steps, None =
         # off (the reference's step); ema_rampup caps the half-life at ema_rampup * step early on (None / 0: constant)
         if ema_halflife is not None and not ema_halflife > 0:
@@ -177,6 +191,21 @@ class TrainStep:
             return
         import torch.distributed as dist
         graphs.eager(lambda: dist.all_reduce(t, op=dist.ReduceOp.SUM, group=self.pg))
+
+    def _gather_captions(self, t32):
+        """(captions of the global batch [world * B, C], this rank's first row): the contrastive CLIP loss's
+        negatives.  Each rank writes its rows into a zero buffer and the buffers are summed -- x + 0 is exact, and
+        the sum all-reduce is the one collective every backend in use here runs on device tensors.  Captions carry
+        no gradient, so nothing comes back.  Once per step; an eager segment of a captured step."""
+        if self.pg is None:
+            return t32, 0
+        import torch.distributed as dist
+        B = t32.shape[0]
+        pos_off = dist.get_rank(self.pg) * B
+        t_all = torch.zeros(self.world * B, t32.shape[1], device=t32.device)
+        t_all[pos_off:pos_off + B].copy_(t32)
+        self._allreduce_sum(t_all)
+        return t_all, pos_off
 
     def _bucketed_grad_allreduce(self, store, begin):
         """Overlapped data-parallel mean of a flat gradient: ``begin()`` arms the engine so
@@ -411,11 +440,17 @@ class TrainStep:
             # onto the adversarial image gradient, clip_weight_8 * dL/d img8 into the new g_img8
             tower = self._clip_tower
             t32 = text.float().contiguous()
+            contrastive = getattr(c, "clip_loss", "cosine") == "contrastive"
+            if contrastive:  # the negatives are the global batch's captions; this rank's are rows pos_off ...
+                t_all, pos_off = self._gather_captions(t32)
             g_img8 = torch.zeros_like(img8)  # (the pad channels stay 0)
             terms = []
             for img, g_out, w, acc_ in ((img16, g_img, c.clip_weight_16, 1), (img8, g_img8, c.clip_weight_8, 0)):
                 feats, cctx = tower.encode_generated(img, save=True)
-                term, g_f = ops.cos_loss(feats, t32, self._clip_scale)
+                if contrastive:
+                    term, g_f = ops.clip_contrast(feats, t_all, c.clip_temperature, self._clip_scale, pos_off=pos_off)
+                else:
+                    term, g_f = ops.cos_loss(feats, t32, self._clip_scale)
                 tower.backward(cctx, g_f, g_out, alpha=w, accumulate=acc_)
                 terms.append(term)
                 cctx = None

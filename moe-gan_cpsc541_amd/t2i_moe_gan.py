@@ -391,14 +391,18 @@ class _ClipLossFn(torch.autograd.Function):
     (moegan_mi/clip_vit.py encode_generated(save=True) / backward); images NCHW [B, 3, R, R], text [B, 512]."""
 
     @staticmethod
-    def forward(ctx, images, text, tower):
+    def forward(ctx, images, text, tower, temperature=None):
         from moegan_mi import ops
         B, _, R, _ = images.shape
         nhwc = torch.zeros(B, R, R, 8, device=images.device, dtype=torch.float32)
         nhwc[..., :3] = images.detach().float().permute(0, 2, 3, 1)
         feats, tctx = tower.encode_generated(nhwc, save=True)
         one = torch.ones(1, device=images.device)
-        loss, g_f = ops.cos_loss(feats, text.detach().float().contiguous(), one)
+        t32 = text.detach().float().contiguous()
+        if temperature is None:
+            loss, g_f = ops.cos_loss(feats, t32, one)
+        else:  # contrastive over the batch's captions, row i's own caption the positive (ops.clip_contrast)
+            loss, g_f = ops.clip_contrast(feats, t32, temperature, one)
         ctx.tower, ctx.tctx, ctx.g_f, ctx.nhwc, ctx.in_dtype = tower, tctx, g_f, nhwc, images.dtype
         return loss.reshape(())
 
@@ -406,18 +410,27 @@ class _ClipLossFn(torch.autograd.Function):
     def backward(ctx, g):
         g_img = torch.zeros_like(ctx.nhwc)
         ctx.tower.backward(ctx.tctx, ctx.g_f, g_img)
-        return (g_img[..., :3].permute(0, 3, 1, 2) * g).to(ctx.in_dtype), None, None
+        return (g_img[..., :3].permute(0, 3, 1, 2) * g).to(ctx.in_dtype), None, None, None
 
 
 class CLIPLoss(nn.Module):
     """Reference :66-119 -- forward-only, no gradient (the image branch runs under no_grad).
     ``differentiable=True`` (this build's extension): ``loss.backward()`` reaches the image through the registered
-    image tower's own backward; it needs the build's tower (load_clip_weights), not a foreign CLIP model."""
+    image tower's own backward; it needs the build's tower (load_clip_weights), not a foreign CLIP model.
+    ``contrastive=True`` (needs ``differentiable=True``): the loss is the softmax cross-entropy of each image against
+    the batch's captions at ``temperature`` (its own caption the positive) instead of 1 - mean cos; 0.07 is CLIP's
+    initial temperature, a choice and not a measurement (the weight loaders drop the checkpoint's logit_scale)."""
 
-    def __init__(self, device=DEVICE, differentiable=False):
+    def __init__(self, device=DEVICE, differentiable=False, contrastive=False, temperature=0.07):
         super().__init__()
         self.device = device
         self.differentiable = bool(differentiable)
+        self.contrastive = bool(contrastive)
+        if self.contrastive and not self.differentiable:
+            raise ValueError("CLIPLoss(contrastive=True) needs differentiable=True")
+        if not float(temperature) > 0 or float(temperature) == float("inf"):
+            raise ValueError(f"temperature must be positive and finite, got {temperature}")
+        self.temperature = float(temperature)
 
     def forward(self, images, text_embeddings):
         if images is None or _clip_model is None:
@@ -428,7 +441,7 @@ class CLIPLoss(nn.Module):
             if tower is None:
                 raise RuntimeError("CLIPLoss(differentiable=True) needs the build's image tower "
                                    "(t2i_moe_gan.load_clip_weights); the registered model has no backward")
-            return _ClipLossFn.apply(images, text_embeddings, tower)
+            return _ClipLossFn.apply(images, text_embeddings, tower, self.temperature if self.contrastive else None)
         with torch.no_grad():
             im = torch.clamp(images, -1, 1)
             if im.shape[-1] != 224 or im.shape[-2] != 224:
@@ -618,7 +631,8 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
                      topk=None, dtype=None, process_group=None, seed=0, resume_from=None, save_every_epoch=False,
                      use_graphs=True, on_batch_done=None, text_tokens=False, max_text_tokens=None, clip_grad=False,
                      ema_kimg=None, ema_rampup=0.05, eval_every=None, eval_samples=None, eval_truncation_psi=1.0,
-                     eval_nearest_k=None, eval_frechet=False, diffaug=None):
+                     eval_nearest_k=None, eval_frechet=False, diffaug=None, clip_contrastive=False,
+                     clip_temperature=0.07):
     """Reference :1029-1669.  ``clip_weight_64``/``clip_weight_32`` (the names train_model.py passes,
     SURVEY.md §0) map to the 16x16 / 8x8 CLIP weights.  ``use_amp`` selects bf16 (the MI355X mixed
     precision; the reference's fp16 GradScaler is not needed) unless ``dtype`` is given.
@@ -643,6 +657,9 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
     ``clip_grad``: the two CLIP terms carry their gradient into the generator (StepConfig.clip_grad; this build's
     extension, the reference's terms are gradient-free): needs the build's image tower registered
     (load_clip_weights); to_rgb_8 then trains and its AdamW state is part of the resume checkpoint.
+    ``clip_contrastive`` (needs ``clip_grad``; off = the cosine terms): the two CLIP terms become the contrastive
+    loss over the global batch's captions at ``clip_temperature`` (StepConfig.clip_loss / clip_temperature; 0.07 is
+    CLIP's initial temperature, a choice and not a measurement); validation's CLIP value stays the cosine.
     ``ema_kimg`` (this build's extension; None = off, the reference's loop): keep an exponential moving average of
     the generator with this half-life in thousands of images (StyleGAN's convention), converted to optimizer steps
     with images per step = dataloader.batch_size x gradient_accumulation_steps x world; ``ema_rampup`` caps the
@@ -720,9 +737,11 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
     if eval_frechet and not eval_every:
         raise ValueError("eval_frechet needs eval_every: it adds to that evaluation")
     # max_resolution 16 is the reference generator; 32 / 64 / 128 train the progressive extension (layout.py)
+    if clip_contrastive and not clip_grad:
+        raise ValueError("clip_contrastive=True needs clip_grad=True (the gradient-free terms stay the cosine)")
     if clip_grad and _clip_model is None:
         raise RuntimeError("clip_grad=True needs the CLIP image tower: call load_clip_weights(path) first")
-    generator = AuroraGenerator(num_experts=num_experts, topk=topk, dtype=dtype, seed=seed,
+    generator =AuroraGenerator(num_experts=num_experts, topk=topk, dtype=dtype, seed=seed,
                                 max_resolution=max_resolution, clip_grad=clip_grad).to(device)
     discriminator = AuroraDiscriminator(dtype=dtype, seed=seed + 1).to(device)
     if checkpoint_activation:
@@ -730,7 +749,8 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
     cfg = StepConfig(E=num_experts, topk=topk, dtype=dtype, r1_gamma=r1_gamma, clip_weight_16=clip_weight_16,
                      clip_weight_8=clip_weight_8, balance_weight=balance_weight, beta1=beta1, beta2=beta2,
                      max_res=max_resolution, clip_grad=clip_grad, ema_halflife=ema_halflife,
-                     ema_rampup=float(ema_rampup) if ema_rampup is not None else None, diffaug=diffaug)
+                     ema_rampup=float(ema_rampup) if ema_rampup is not None else None, diffaug=diffaug,
+                     clip_loss="contrastive" if clip_contrastive else "cosine", clip_temperature=clip_temperature)
     # CLIP terms of the generator loss (logging / guard only unless clip_grad: no gradient, :98-101)
     ts = TrainStep(cfg, device, process_group=process_group, gstore=generator._store, dstore=discriminator._store,
                    clip_encoder=_clip_model.encode_image if _clip_model is not None else None)

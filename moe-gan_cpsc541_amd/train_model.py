@@ -91,6 +91,11 @@ def parse_args(argv=None):
                         "as in the reference, unless --clip_grad)")
     p.add_argument("--clip_grad", action="store_true",
                    help="the CLIP terms train the generator (image-tower backward); needs --clip_weights")
+    p.add_argument("--clip_contrastive", action="store_true",
+                   help="with --clip_grad: the CLIP terms are a contrastive loss over the batch's captions (the "
+                        "image's own caption the positive) instead of 1 - cos")
+    p.add_argument("--clip_temperature", type=float, default=0.07,
+                   help="with --clip_contrastive: the softmax temperature (default: CLIP's initial 0.07)")
     p.add_argument("--hyperparameters", type=str, default=None,
                    help="SageMaker-style hyperparameters.json (string values, sagemaker_train.py:85-102); batch_size "
                         "and the train_aurora_gan keys override the flags above, other keys are reported as unused")
@@ -130,6 +135,10 @@ def parse_args(argv=None):
             p.error(f"--diffaug: {e}")
     if args.clip_grad and not args.clip_weights:
         p.error("--clip_grad needs --clip_weights (the CLIP image tower whose backward it runs)")
+    if args.clip_contrastive and not args.clip_grad:
+        p.error("--clip_contrastive needs --clip_grad (it replaces the term whose gradient trains the generator)")
+    if not args.clip_temperature > 0 or args.clip_temperature == float("inf"):
+        p.error("--clip_temperature must be positive and finite")
     if args.eval_every and not args.clip_weights:
         p.error("--eval_every needs --clip_weights (the CLIP image tower whose features it compares)")
     if args.eval_nearest_k is not None and not args.eval_every:
@@ -213,6 +222,9 @@ def main(argv=None):
         kw.update(text_tokens=True, max_text_tokens=args.max_text_tokens)
     if args.clip_grad:
         kw.update(clip_grad=True)
+    if args.clip_contrastive:
+        kw.setdefault("clip_contrastive", True)
+        kw.setdefault("clip_temperature", args.clip_temperature)
     if args.ema_kimg is not None:
         kw.setdefault("ema_kimg", args.ema_kimg)
         kw.setdefault("ema_rampup", args.ema_rampup)
