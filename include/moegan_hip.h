@@ -116,10 +116,48 @@ const char* mg_source_hash(void);
 int mg_set_workspace(void* ptr, size_t bytes, void* stream);
 int mg_workspace_reserve(size_t bytes, void* stream);
 int64_t mg_workspace_bytes(void* stream);
-/* Tuning override for measurements (key: 0 conv-wgrad tile, 1 grouped-wgrad tile, 2 conv tile,
-   3 gemm tile [64 | 128], 4 conv-wgrad splits, 5 disable split-K slabs, 6 enable the XCD-aware tile
-   order, 29 keep the modulated conv's gx / gs out of the data gradient's epilogue; value 0 = automatic). */
+/* Tuning slots: the A/B switches and numeric knobs every kernel-form decision reads (process-wide, atomic; value 0 =
+   automatic in every slot).  The numbers are ABI (MOEGAN_TUNE="slot=value" specs name them) and never change; a
+   retired slot keeps its number and accepts only 0. */
+enum {
+  MG_TUNE_WGRAD_TILE = 0,          /* conv weight-gradient tile: 64 | 128 | 256 (256 x 128) | 257 (128 x 256) */
+  MG_TUNE_GWGRAD_TILE = 1,         /* grouped weight-gradient tile: 64 keeps 64^2 where 128^2 would be taken */
+  MG_TUNE_CONV_TILE = 2,           /* implicit-conv tile: 64 | 128 | 256 (256 x 128) | 257 (128 x 256) */
+  MG_TUNE_GEMM_TILE = 3,           /* GEMM tile: 64 | 128 | 257 (128 x 256) */
+  MG_TUNE_WGRAD_SPLITS = 4,        /* conv weight-gradient split count, > 0: that many */
+  MG_TUNE_NO_SLABS = 5,            /* 1: no split-K slabs for the few-tile GEMMs / convs */
+  MG_TUNE_XCD = 6,                 /* XCD-aware tile order: 0 automatic (= every launch), 1 every launch, 2 split-K only, 3 none */
+  MG_TUNE_WGRAD_MODE = 7,          /* conv weight gradients: 0 fp32 slabs + reduction, otherwise split K meeting in atomics */
+  MG_TUNE_RETIRED_8 = 8,           /* retired: LDS-staged warp / offset-head backward (measured slower; removed) */
+  MG_TUNE_SHORTK = 9,              /* 2: one-K-step GEMMs follow the size rule instead of 64^2 tiles */
+  MG_TUNE_ATOMIC_BLOCKS = 10,      /* atomic split-K GEMMs: grid target (blocks), 0 automatic (512) */
+  MG_TUNE_DETERMINISTIC = 11,      /* 1: every cross-workgroup reduction in a fixed order (bit-reproducible, slower) */
+  MG_TUNE_S1_OFF = 12,             /* 1: weight gradients of stride-1 convs through the generic LdMCConv (A/B) */
+  MG_TUNE_D0_STORE = 13,           /* mg_d0_fwd output path: 0 automatic, 1 straight from the accumulators, 2 LDS-staged rows */
+  MG_TUNE_FFN_BWD_OCC = 14,        /* mg_moe_ffn_bwd: 0 automatic (one block per CU, 256 VGPRs, 128-unit chunks), 2 two blocks (128 VGPRs), 3 64-unit chunks */
+  MG_TUNE_WIDE_WGRAD = 15,         /* 1: long-reduction weight gradients through the generic split-K GEMM (A/B), 2: mg_wgrad_wide.hip on every eligible shape, 3: the same (128^2 tiles), 4: 256^2 tiles where M, N >= 256 */
+  MG_TUNE_NARROW = 16,             /* the 32-channel 3x3 convs (offset heads) through the implicit GEMM: 1 all, 2 fwd, 3 dgrad, 4 wgrad */
+  MG_TUNE_NARROW_BLOCKS = 17,      /* mg_narrow.hip grid target (blocks): 0 automatic */
+  MG_TUNE_DISPATCH3 = 18,          /* 1: mg_moe_dispatch as count / scan / scatter (A/B; default count + scatter-scan) */
+  MG_TUNE_NARROW_WPX = 19,         /* 4: offset-head forward on 256-pixel tiles (four pixel fragments per wave; A/B) */
+  MG_TUNE_GWGRAD_BLOCKS = 20,      /* mg_gemm_grouped_wgrad split target (blocks of 128^2 tiles): 0 automatic (512) */
+  MG_TUNE_BATCH_SPLIT = 21,        /* mg_gemm_batch split-K slabs, > 1: on, that block target (A/B; 0 / 1 off: neutral in the step) */
+  MG_TUNE_GROUPED_SHORTK = 22,     /* grouped expert GEMMs with K <= this on 64^2 tiles (0: 512, -1: never) */
+  MG_TUNE_RETIRED_23 = 23,         /* retired: split-K slabs reduced inside the launch (measured slower; removed) */
+  MG_TUNE_ROUTER_TEAM = 24,        /* A/B bitmask, lane-FMA forms instead of the MFMA / team ones: 1 router logits, 2 router backward (thread per token), 4 token gradient */
+  MG_TUNE_ADAMW_CACHED = 25,       /* 1: AdamW streams through the caches (A/B; default non-temporal loads / stores) */
+  MG_TUNE_ATOMIC_MINK = 26,        /* atomic split-K GEMMs: the least K per split (0: automatic, 256) */
+  MG_TUNE_WIDE_BLOCKS = 27,        /* mg_wgrad_wide.hip grid target (blocks): 0 automatic (256) */
+  MG_TUNE_WGRAD_SLAB_BLOCKS = 28,  /* conv weight-gradient slab split target (blocks): 0 automatic (1024) */
+  MG_TUNE_MODGRAD_UNFUSED = 29,    /* 1: the modulated conv's gx / gs as mg_modconv_bwd_in after the data-gradient GEMM, never in its epilogue (A/B) */
+  MG_TUNE_WGRAD_BIAS_UNFUSED = 30, /* 1: bias gradients by the separate column sums, never from the weight-gradient kernels' K loop (A/B) */
+  MG_TUNE_COUNT = 31
+};
+/* mg_set_tuning: set slot `key` (an MG_TUNE_* number) for measurements; a key out of range, or a value other than 0 on
+   a retired slot, is MG_ERR_ARG.  mg_get_tuning: the slot's current value, or MG_ERR_ARG (and the error text) for a
+   key out of range -- read it before an override to restore what was there. */
 int mg_set_tuning(int key, int value);
+int mg_get_tuning(int key);
 
 /* Measurement of one call inside a training step (bench.py's roofline kernel; no reference
    counterpart: the reference times nothing below the Python loop, t2i_moe_gan.py:1262-1421).

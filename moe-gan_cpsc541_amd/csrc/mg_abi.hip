@@ -1,7 +1,6 @@
 // Error plumbing, scratch workspace, tuning switches and version of libmoegan_hip.
 #include <atomic>
 #include <mutex>
-#include <vector>
 #include <string>
 
 #include "mg_common.h"
@@ -77,39 +76,6 @@ void* mg_workspace(size_t bytes, hipStream_t stream) {
   return e->ptr;
 }
 
-namespace {
-struct CntEntry {
-  int device;
-  hipStream_t stream;
-  int* ptr;
-  int n;
-};
-std::vector<CntEntry> g_cnt;
-std::mutex g_cnt_mu;
-}  // namespace
-
-int* mg_tile_counters(int n, hipStream_t stream) {
-  int dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
-  std::lock_guard<std::mutex> lk(g_cnt_mu);
-  for (auto& e : g_cnt)
-    if (e.device == dev && e.stream == stream && e.n >= n) return e.ptr;
-  hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-  if (hipStreamIsCapturing(stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone) return nullptr;
-  const int want = std::max(n, 8192);
-  int* p = nullptr;
-  if (hipMalloc(reinterpret_cast<void**>(&p), (size_t)want * sizeof(int)) != hipSuccess) return nullptr;
-  if (hipMemsetAsync(p, 0, (size_t)want * sizeof(int), stream) != hipSuccess) return nullptr;
-  for (auto& e : g_cnt)
-    if (e.device == dev && e.stream == stream) {  // a larger set replaces the old one (kept: in-flight launches)
-      e.ptr = p;
-      e.n = want;
-      return p;
-    }
-  g_cnt.push_back(CntEntry{dev, stream, p, want});
-  return p;
-}
-
 extern "C" int mg_set_workspace(void* ptr, size_t bytes, void* stream) {
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return MG_ERR_LAUNCH;
@@ -150,8 +116,21 @@ extern "C" int mg_set_tuning(int key, int value) {
     mg_set_error("mg_set_tuning: key out of range");
     return MG_ERR_ARG;
   }
+  // a removed variant must fail loudly, not measure the default
+  if ((key == MG_TUNE_RETIRED_8 || key == MG_TUNE_RETIRED_23) && value != 0) {
+    mg_set_error("mg_set_tuning: slot " + std::to_string(key) + " is retired (its variant was removed): only 0 is accepted");
+    return MG_ERR_ARG;
+  }
   g_mg_tune[key].store(value, std::memory_order_relaxed);
   return MG_OK;
+}
+
+extern "C" int mg_get_tuning(int key) {
+  if (key < 0 || key >= MG_TUNE_COUNT) {
+    mg_set_error("mg_get_tuning: key out of range");
+    return MG_ERR_ARG;
+  }
+  return g_mg_tune[key].load(std::memory_order_relaxed);
 }
 
 extern "C" const char* mg_last_error(void) { return g_last_error.c_str(); }

@@ -151,9 +151,6 @@ int mg_check_launch(const char* what);
 // Device scratch, one block per (device, stream): caller-owned (mg_set_workspace) or library-owned
 // (grown on demand, never shrunk).  NULL when it cannot be provided (mg_last_error says why).
 void* mg_workspace(size_t bytes, hipStream_t stream);
-// per-stream zeroed int counters for in-launch split-K reductions (mg_gemm.h gemm_splitk_fused_kernel): at least n,
-// allocated and zeroed outside stream capture only (NULL otherwise: the caller takes the two-launch form)
-int* mg_tile_counters(int n, hipStream_t stream);
 // Gradient folds (mg_fold.hip).  A producer of fold partials asks mg_fold_alloc first: non-NULL = the stream defers
 // its folds (mg_fold_defer) and the partials live in the deferral arena until the flush, so the fold is recorded
 // (deferred = true); NULL = take mg_workspace and fold now.  Both paths run the same fold kernels.

@@ -105,7 +105,6 @@ template <typename T, typename TO, bool X3>
 bool run_splitk_slabs(const Plan& p, int a_kc, int b_kc, int M, int N, int K, const void* A, int64_t lda,
                       const void* B, int64_t ldb, void* C, int64_t ldc, const mg_epilogue* e, hipStream_t st) {
   const int splits = p.splits, kchunk = p.kchunk;
-  const int64_t tiles = (int64_t)cdiv(M, 64) * cdiv(N, 64);
   const int64_t MN = (int64_t)M * N;
   float* ws = reinterpret_cast<float*>(mg_workspace((size_t)splits * MN * sizeof(float), st));
   if (!ws) return false;
@@ -116,20 +115,11 @@ bool run_splitk_slabs(const Plan& p, int a_kc, int b_kc, int M, int N, int K, co
   slab.vec_ok = slab.host_vec_ok() ? 1 : 0;
   auto ep = make_epi<TO>(C, ldc, e);
   ep.vec_ok = ep.host_vec_ok() ? 1 : 0;
-  // the reduction inside the launch (last-arriving split of each tile; A/B slot MG_TUNE_SPLITK_FUSED): measured at
-  // C2 no faster on the few-tile GEMMs (the agent-scope release / acquire cost what the second launch did) and
-  // 30-70 % slower on the many-tile conv slabs (every block's release writes back its XCD's dirty L2 lines)
-  int* cnt = g_mg_tune[MG_TUNE_SPLITK_FUSED] == 1 ? mg_tile_counters((int)tiles, st) : nullptr;
   auto go = [&](auto la, auto lb, auto akc, auto bkc) {
     dim3 grid(cdiv(M, 64), cdiv(N, 64), splits);
-    if (cnt)
-      hipLaunchKernelGGL((gemm_splitk_fused_kernel<T, 64, 64, decltype(akc)::value, decltype(bkc)::value,
-                                                  decltype(la), decltype(lb), TO, X3>),
-                         grid, dim3(NTHREADS), 0, st, la, lb, slab, ep, M, N, K, kchunk, cnt);
-    else
-      hipLaunchKernelGGL((gemm_kernel<T, 64, 64, decltype(akc)::value, decltype(bkc)::value, decltype(la),
-                                      decltype(lb), Epi<float>, 0, X3>),
-                         grid, dim3(NTHREADS), 0, st, la, lb, slab, M, N, K, kchunk, xcd_group());
+    hipLaunchKernelGGL((gemm_kernel<T, 64, 64, decltype(akc)::value, decltype(bkc)::value, decltype(la),
+                                    decltype(lb), Epi<float>, 0, X3>),
+                       grid, dim3(NTHREADS), 0, st, la, lb, slab, M, N, K, kchunk, xcd_group());
   };
   const T* Ap = reinterpret_cast<const T*>(A);
   const T* Bp = reinterpret_cast<const T*>(B);
@@ -144,7 +134,6 @@ bool run_splitk_slabs(const Plan& p, int a_kc, int b_kc, int M, int N, int K, co
     if (b_kc) go(la, LdKC<T>{Bp, ldb, N, K, nullptr, 1, nullptr, 0}, FF{}, TT{});
     else go(la, LdMC<T>{Bp, ldb, N, K, nullptr, 1, nullptr, 0}, FF{}, FF{});
   }
-  if (cnt) return true;
   int blocks = (int)std::min<int64_t>(cdiv(MN, 256), 2048);
   hipLaunchKernelGGL((splitk_reduce_kernel<Epi<TO>>), dim3(blocks), dim3(256), 0, st, ws, splits, M, N, ep);
   return true;
@@ -378,7 +367,6 @@ bool conv_slabs_t(const Plan& p, const void* x, int B, int H, int W, int Cin, co
                   int KW, int stride, int pad, void* y, int64_t ldy, const mg_epilogue* e, hipStream_t st) {
   int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
   int M = B * OH * OW, K = KH * KW * Cin;
-  int64_t tiles = (int64_t)cdiv(M, BM) * cdiv(Cout, BN);
   const int splits = p.splits, kchunk = p.kchunk;
   const int64_t MN = (int64_t)M * Cout;
   float* ws = reinterpret_cast<float*>(mg_workspace((size_t)splits * MN * sizeof(float), st));
@@ -394,12 +382,6 @@ bool conv_slabs_t(const Plan& p, const void* x, int B, int H, int W, int Cin, co
   dim3 grid(cdiv(M, BM), cdiv(Cout, BN), splits);
   auto ep = make_epi<TO>(y, ldy, e);
   ep.vec_ok = ep.host_vec_ok() ? 1 : 0;
-  int* cnt = g_mg_tune[MG_TUNE_SPLITK_FUSED] == 1 ? mg_tile_counters((int)tiles, st) : nullptr;
-  if (cnt) {  // the reduction inside the launch (gemm_splitk_fused_kernel; A/B only, see run_splitk_slabs)
-    hipLaunchKernelGGL((gemm_splitk_fused_kernel<T, BM, BN, true, true, LdKCConv<T, false, SC>, LdKC<T>, TO>), grid,
-                       dim3(NTHREADS), 0, st, la, lb, slab, ep, M, Cout, K, kchunk, cnt);
-    return true;
-  }
   hipLaunchKernelGGL((gemm_kernel<T, BM, BN, true, true, LdKCConv<T, false, SC>, LdKC<T>, Epi<float>>), grid,
                      dim3(NTHREADS), 0, st, la, lb, slab, M, Cout, K, kchunk, xcd_group());
   int blocks = (int)std::min<int64_t>(cdiv(MN, 256), 2048);

@@ -9,33 +9,11 @@
 #include <algorithm>
 #include <atomic>
 
+#include "../../include/moegan_hip.h"
+
 typedef uint16_t bf16_t;  // raw bf16 storage (activations in bf16 mode)
 
-// Tuning overrides (0 = automatic), set through mg_set_tuning for A/B measurements.
-enum { MG_TUNE_WGRAD_TILE = 0, MG_TUNE_GWGRAD_TILE = 1, MG_TUNE_CONV_TILE = 2, MG_TUNE_GEMM_TILE = 3,
-       MG_TUNE_WGRAD_SPLITS = 4, MG_TUNE_NO_SLABS = 5, MG_TUNE_XCD = 6 /* 0 auto (= all), 1 all, 2 split-K, 3 none */, MG_TUNE_WGRAD_MODE = 7,
-       MG_TUNE_WARP_LDS = 8, MG_TUNE_SHORTK = 9, MG_TUNE_ATOMIC_BLOCKS = 10, MG_TUNE_DETERMINISTIC = 11,
-       MG_TUNE_S1_OFF = 12,  // 1: weight gradients of stride-1 convs through the generic LdMCConv (A/B)
-       MG_TUNE_D0_STORE = 13,  // mg_d0_fwd output path: 0 automatic, 1 straight from the accumulators, 2 LDS-staged rows
-       MG_TUNE_FFN_BWD_OCC = 14,  // mg_moe_ffn_bwd: 0 automatic (one block per CU, 256 VGPRs, 128-unit chunks), 2 two blocks (128 VGPRs), 3 64-unit chunks
-       MG_TUNE_WIDE_WGRAD = 15,   // 1: long-reduction weight gradients through the generic split-K GEMM (A/B), 2: mg_wgrad_wide.hip on every eligible shape, 3: the same (128^2 tiles), 4: 256^2 tiles where M, N >= 256
-       MG_TUNE_NARROW = 16,  // the 32-channel 3x3 convs (offset heads) through the implicit GEMM: 1 all, 2 fwd, 3 dgrad, 4 wgrad
-       MG_TUNE_NARROW_BLOCKS = 17,  // mg_narrow.hip grid target (blocks): 0 automatic
-       MG_TUNE_DISPATCH3 = 18,  // 1: mg_moe_dispatch as count / scan / scatter (A/B; default count + scatter-scan)
-       MG_TUNE_NARROW_WPX = 19,  // 4: offset-head forward on 256-pixel tiles (four pixel fragments per wave; A/B)
-       MG_TUNE_GWGRAD_BLOCKS = 20,  // mg_gemm_grouped_wgrad split target (blocks of 128^2 tiles): 0 automatic (512)
-       MG_TUNE_BATCH_SPLIT = 21,  // mg_gemm_batch split-K slabs, > 1: on, that block target (A/B; 0 / 1 off: neutral in the step)
-       MG_TUNE_GROUPED_SHORTK = 22,  // grouped expert GEMMs with K <= this on 64^2 tiles (0: 512, -1: never)
-       MG_TUNE_SPLITK_FUSED = 23,    // 1: split-K slabs reduced inside the launch (measured slower at C2: off)
-       MG_TUNE_ROUTER_TEAM = 24,     // A/B bitmask, lane-FMA forms instead of the MFMA / team ones: 1 router
-                                     // logits, 2 router backward (thread per token), 4 token gradient
-       MG_TUNE_ADAMW_CACHED = 25,    // 1: AdamW streams through the caches (A/B; default non-temporal loads / stores)
-       MG_TUNE_ATOMIC_MINK = 26,     // atomic split-K GEMMs: the least K per split (0: automatic)
-       MG_TUNE_WIDE_BLOCKS = 27,     // mg_wgrad_wide.hip grid target (blocks): 0 automatic (256)
-       MG_TUNE_WGRAD_SLAB_BLOCKS = 28,  // conv weight-gradient slab split target (blocks): 0 automatic (1024)
-       MG_TUNE_MODGRAD_UNFUSED = 29,  // 1: the modulated conv's gx / gs as mg_modconv_bwd_in after the data-gradient GEMM, never in its epilogue (A/B)
-       MG_TUNE_WGRAD_BIAS_UNFUSED = 30,  // 1: bias gradients by the separate column sums, never from the weight-gradient kernels' K loop (A/B)
-       MG_TUNE_COUNT = 31 };
+// The tuning slots (MG_TUNE_*, 0 = automatic) are tabled in the public header, next to mg_set_tuning.
 extern std::atomic<int> g_mg_tune[MG_TUNE_COUNT];
 // Deterministic mode (mg_set_tuning(MG_TUNE_DETERMINISTIC, 1)): every reduction that crosses workgroups runs in
 // a fixed order -- per-block partial rows in the stream's workspace folded by one pass, or one writer per

@@ -107,8 +107,17 @@ def _parse_header(path=_HEADER):
     return sigs
 
 
+def _parse_tune(path=_HEADER):
+    """{name: number} of the live tuning slots: the header's MG_TUNE_* enum without the prefix, COUNT and the retired
+    entries (mg_set_tuning refuses those) left out."""
+    import re
+    table = {n: int(v) for n, v in re.findall(r"\bMG_TUNE_(\w+)\s*=\s*(\d+)\s*,", open(path).read())}
+    return {n: v for n, v in table.items() if not n.startswith("RETIRED_")}
+
+
 ARGNAMES = {}  # entry point -> parameter names, in order (the roofline attribution reads shapes by name)
 _SIGS = _parse_header()
+TUNE = _parse_tune()
 EP = ctypes.POINTER(Epilogue)
 
 _lib = None

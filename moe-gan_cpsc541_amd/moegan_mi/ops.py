@@ -4,6 +4,7 @@ Every function enqueues on torch's current stream and returns its output
 tensor(s).  Shapes follow include/moegan_hip.h: activations are NHWC/token
 rows, weights are in the reference layout unless a ``pack`` says otherwise.
 """
+import contextlib
 import ctypes
 import math
 
@@ -17,14 +18,32 @@ call, ptr, dt, S = L.call, L.ptr, L.dt, L.stream
 E = L.epilogue
 
 
-TUNE_DETERMINISTIC = 11  # mg_common.h MG_TUNE_DETERMINISTIC
+@contextlib.contextmanager
+def tuning(**slots):
+    """Scoped override of the library's tuning slots (the MG_TUNE_* table in include/moegan_hip.h, names without the
+    prefix): ``with ops.tuning(ROUTER_TEAM=4, DETERMINISTIC=1): ...``.  On exit every slot returns to the value it
+    held on entry (a session-wide MOEGAN_TUNE override included), whether or not the block raised."""
+    unknown = [n for n in slots if n not in L.TUNE]
+    if unknown:
+        raise L.MGError(f"unknown tuning slot {unknown}: one of {sorted(L.TUNE)}")
+    saved = []
+    try:
+        for name, value in slots.items():
+            key = L.TUNE[name]
+            old = L.lib().mg_get_tuning(key)
+            call("mg_set_tuning", key, value)
+            saved.append((key, old))
+        yield
+    finally:
+        for key, old in reversed(saved):
+            call("mg_set_tuning", key, old)
 
 
 def set_deterministic(on=True):
     """Deterministic mode of the library: every cross-workgroup reduction of the step in a fixed
     order (partial rows + one fold, or one writer per element) instead of fp32 atomics, so two identically
     initialised steps give bit-identical results; slower.  Process-wide, like torch's own switch."""
-    call("mg_set_tuning", TUNE_DETERMINISTIC, 1 if on else 0)
+    call("mg_set_tuning", L.TUNE["DETERMINISTIC"], 1 if on else 0)
 
 
 def _ld(t):
@@ -318,9 +337,6 @@ def conv2d_mx8(xq, xsc, wq, wsc, Cout, KH, KW, stride=1, pad=0, out=None, out_dt
            lambda: call("mg_conv2d_fwd_mx8", ptr(x), ptr(xsc), B, H, W, Cin, ptr(wq), ptr(wsc), Cout, KH, KW, stride, pad,
                         ptr(out), ldy or out.shape[-1], dt(out), ep, S()))
     return out
-
-
-TUNE_WGRAD_BIAS_UNFUSED = 30  # mg_common.h MG_TUNE_WGRAD_BIAS_UNFUSED: 1 keeps the bias gradients on the column sums
 
 
 def conv2d_wgrad(gy, x, Cout, KH, KW, stride, pad, gw, in_scale=None, ldg=None, splits=0, bias_grad=None):
@@ -754,9 +770,6 @@ def modconv_bwd_in(gxt, x, s, B, HW, Cin, gx, gs, accumulate=0):
     call("mg_modconv_bwd_in", dt(gxt), ptr(gxt), gxt.stride(0), dt(x), ptr(x), x.stride(0), ptr(s), s.stride(0), B, HW,
          Cin, dt(gx) if gx is not None else 0, ptr(gx), gx.stride(0) if gx is not None else 0, accumulate, ptr(gs),
          S())
-
-
-TUNE_MODGRAD_UNFUSED = 29  # mg_common.h MG_TUNE_MODGRAD_UNFUSED: 1 keeps gx / gs out of the data gradient's epilogue
 
 
 def modconv_dgrad_fusable(gyt, k, B, H, W, Cin, x, s, gx):

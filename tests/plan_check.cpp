@@ -48,7 +48,7 @@ static void check_plan(const Plan& p, bool bf16, bool x3, bool conv, int K) {
   }
 }
 
-static void structural(int slot, int value) {
+static void structural(const char* slot, int value) {
   for (int dt = 0; dt < 3; ++dt) {  // bf16, fp32, fp32 multiplied as split bf16
     const bool bf16 = dt == 0, x3 = dt == 2;
     for (int M : {8, 48, 256, 8192, 16384, 65536})
@@ -57,7 +57,7 @@ static void structural(int slot, int value) {
           for (int form = 0; form < 5; ++form) {  // plain; atomic, automatic splits; atomic, 4 splits; A transform; QuickGELU'
             const GemmEpi e{form == 1 || form == 2, form == 3, form == 4};
             const int splits = form == 1 ? 0 : form == 2 ? 4 : 1;
-            std::snprintf(g_ctx, sizeof g_ctx, "slot %d=%d gemm dt %d %d x %d x %d form %d", slot, value, dt, M, N, K, form);
+            std::snprintf(g_ctx, sizeof g_ctx, "%s=%d gemm dt %d %d x %d x %d form %d", slot, value, dt, M, N, K, form);
             const Plan p = plan_gemm(bf16, x3, M, N, K, e, splits);
             check_plan(p, bf16, x3, false, K);
             if (x3 || e.xf) CHECK(is(p, 64, 64) && is_fb(p, 64, 64));
@@ -74,7 +74,7 @@ static void structural(int slot, int value) {
           for (int Cout : {8, 24, 32, 128, 256, 1024})
             for (int form = 0; form < 4; ++form) {  // 3x3 / s1 / p1: plain, in_scale, atomic; 4x4 / s2 / p1
               const int k = form == 3 ? 4 : 3, stride = form == 3 ? 2 : 1;
-              std::snprintf(g_ctx, sizeof g_ctx, "slot %d=%d conv dt %d B %d %dx%d %d -> %d form %d", slot, value, dt, B, H, H,
+              std::snprintf(g_ctx, sizeof g_ctx, "%s=%d conv dt %d B %d %dx%d %d -> %d form %d", slot, value, dt, B, H, H,
                             Cin, Cout, form);
               const Plan p = plan_conv_fwd(bf16, B, H, H, Cin, Cout, k, k, stride, 1, form == 1, form == 2);
               check_plan(p, bf16, false, true, k * k * Cin);
@@ -130,17 +130,21 @@ static void anchors() {  // the measurements quoted next to the rules in mg_plan
 }
 
 int main() {
-  static const int settings[][2] = {{0, 0},   {5, 1},   {3, 64},  {3, 128}, {3, 257}, {2, 64},
-                                    {2, 128}, {2, 256}, {2, 257}, {9, 2},   {11, 1}};
+#define SLOT(name, value) {MG_TUNE_##name, #name, value}
+  static const struct { int slot; const char* name; int value; } settings[] = {
+      SLOT(WGRAD_TILE, 0) /* default tuning */, SLOT(NO_SLABS, 1), SLOT(GEMM_TILE, 64), SLOT(GEMM_TILE, 128),
+      SLOT(GEMM_TILE, 257), SLOT(CONV_TILE, 64), SLOT(CONV_TILE, 128), SLOT(CONV_TILE, 256), SLOT(CONV_TILE, 257),
+      SLOT(SHORTK, 2), SLOT(DETERMINISTIC, 1)};
+#undef SLOT
   for (const auto& s : settings) {
-    g_mg_tune[s[0]] = s[1];
-    structural(s[0], s[1]);
-    g_mg_tune[s[0]] = 0;
+    g_mg_tune[s.slot] = s.value;
+    structural(s.name, s.value);
+    g_mg_tune[s.slot] = 0;
   }
   anchors();
-  // the one place the fused and the plain 1x1 data gradient used to part: slot 9 = 2 takes the size rule at K <= BK
+  // the one place the fused and the plain 1x1 data gradient used to part: SHORTK = 2 takes the size rule at K <= BK
   g_mg_tune[MG_TUNE_SHORTK] = 2;
-  std::snprintf(g_ctx, sizeof g_ctx, "slot 9=2");
+  std::snprintf(g_ctx, sizeof g_ctx, "SHORTK=2");
   CHECK(is(plan_gemm(true, false, 8192, 8192, 48, GemmEpi{false, false, false}, 1), 128, 256));
   g_mg_tune[MG_TUNE_SHORTK] = 0;
   std::printf("%d plans, %d of them slabs, %d failures\n", g_plans, g_slabs, g_fail);

@@ -41,29 +41,28 @@ CASES = [(4, 64, "nchw"), (2, 64, 4), (3, 16, 8), (1, 16, "nchw"), (2, 128, "nch
 @pytest.mark.parametrize("store", [0, 2])
 @pytest.mark.parametrize("B,H,layout", CASES)
 def test_d0_forward_and_r1_pass(B, H, layout, store):
-    """``store``: the output path (tuning slot MG_TUNE_D0_STORE: 0 automatic, 2 LDS-staged rows)."""
+    """``store``: the output path (tuning slot 13, D0_STORE: 0 automatic, 2 LDS-staged rows)."""
     from moegan_mi import _lib as L
     from moegan_mi import ops
-    L.call("mg_set_tuning", 13, store)
-    g = torch.Generator(device=DEV).manual_seed(B * 1000 + H)
-    x, strides, xr = _img(B, H, layout, g)
-    w0p, w = _w0(g)
-    bias = torch.randn(128, device=DEV, generator=g) * 0.1
-    h0 = ops.d0_fwd(x, strides, B, H, H, w0p, bias=bias)
-    cols = ops.im2col_4x4s2(x, strides, B, H, H, 3, 48, torch.bfloat16)
-    h0_ref = ops.linear(cols, w0p, bias=bias, act=L.ACT_LRELU).view(B, H // 2, H // 2, 128)
-    torch.cuda.synchronize()
-    assert torch.equal(h0, h0_ref), float((h0.float() - h0_ref.float()).abs().max())
-    # plain fp32 torch on the same bf16 operands
-    t = F.leaky_relu(F.conv2d(xr.bfloat16().float(), w, bias, stride=2, padding=1), 0.2).permute(0, 2, 3, 1)
-    assert float((h0.float() - t).abs().max()) <= 1e-2 * float(t.abs().max())
-    # R1 forward-mode pass: conv(u) * LeakyReLU'(h0), no bias
-    m = ops.d0_fwd(x, strides, B, H, H, w0p, aux=h0)
-    m_ref = torch.empty_like(m)
-    ops.gemm(cols, w0p, cols.shape[0], 128, 48, out=m_ref.view(-1, 128),
-             ep=ops.E(act=L.ACT_MUL_LRELU_GRAD, aux=h0, ld_aux=128))
-    torch.cuda.synchronize()
-    L.call("mg_set_tuning", 13, 0)
+    with ops.tuning(D0_STORE=store):
+        g = torch.Generator(device=DEV).manual_seed(B * 1000 + H)
+        x, strides, xr = _img(B, H, layout, g)
+        w0p, w = _w0(g)
+        bias = torch.randn(128, device=DEV, generator=g) * 0.1
+        h0 = ops.d0_fwd(x, strides, B, H, H, w0p, bias=bias)
+        cols = ops.im2col_4x4s2(x, strides, B, H, H, 3, 48, torch.bfloat16)
+        h0_ref = ops.linear(cols, w0p, bias=bias, act=L.ACT_LRELU).view(B, H // 2, H // 2, 128)
+        torch.cuda.synchronize()
+        assert torch.equal(h0, h0_ref), float((h0.float() - h0_ref.float()).abs().max())
+        # plain fp32 torch on the same bf16 operands
+        t = F.leaky_relu(F.conv2d(xr.bfloat16().float(), w, bias, stride=2, padding=1), 0.2).permute(0, 2, 3, 1)
+        assert float((h0.float() - t).abs().max()) <= 1e-2 * float(t.abs().max())
+        # R1 forward-mode pass: conv(u) * LeakyReLU'(h0), no bias
+        m = ops.d0_fwd(x, strides, B, H, H, w0p, aux=h0)
+        m_ref = torch.empty_like(m)
+        ops.gemm(cols, w0p, cols.shape[0], 128, 48, out=m_ref.view(-1, 128),
+                 ep=ops.E(act=L.ACT_MUL_LRELU_GRAD, aux=h0, ld_aux=128))
+        torch.cuda.synchronize()
     assert torch.equal(m, m_ref), float((m.float() - m_ref.float()).abs().max())
 
 

@@ -4,7 +4,8 @@ E = 4 / 8 / 16 / 32 (C2: 8, C5: 32), k = 1 / 2 / 4, ragged chunk tails (the kern
 chunks), experts that receive no assignment, the skewed routing of an early-training router, and a size whose
 chunk-count table exceeds the parallel scan's LDS table (the serial scan then runs), and the largest table the parallel scan takes
 (E=32, k=4, T=131072: 512 chunks x 32 = 16384 counts, ~70 KB of dynamic LDS, within gfx950's 160 KB per CU).
-Both launch forms: count + scatter-with-folded-scan (default) and count / scan / scatter (tuning slot 18 = 1)."""
+Both launch forms: count + scatter-with-folded-scan (default) and count / scan / scatter (tuning slot 18,
+DISPATCH3 = 1)."""
 import pytest
 import torch
 
@@ -30,7 +31,6 @@ def _reference(topi, gate, E, bm):
                                         (32, 4, 131072, False)])
 @pytest.mark.parametrize("three", [0, 1])
 def test_dispatch_matches_stable_sort(E, k, T, skew, three):
-    from moegan_mi import _lib as L
     from moegan_mi import ops
     g = torch.Generator(device=DEV).manual_seed(E * 1000 + k * 10 + T)
     if skew:  # a few experts take most tokens; the upper half of the experts gets none
@@ -41,12 +41,9 @@ def test_dispatch_matches_stable_sort(E, k, T, skew, three):
         scores = torch.rand(T, E, device=DEV, generator=g)
     topi = scores.topk(k, dim=1).indices.int().contiguous()
     gate = torch.rand(T, k, device=DEV, generator=g)
-    L.call("mg_set_tuning", 18, three)
-    try:
+    with ops.tuning(DISPATCH3=three):
         row_off, tile_off, perm, pos_of, gate_pos = ops.moe_dispatch(topi, gate, E)
         torch.cuda.synchronize()
-    finally:
-        L.call("mg_set_tuning", 18, 0)
     r_row, r_tile, r_perm, r_pos, r_gate = _reference(topi, gate, E, 128)
     assert torch.equal(row_off.cpu().long(), r_row)
     assert torch.equal(tile_off.cpu().long(), r_tile)

@@ -35,6 +35,36 @@ def test_binding_matches_header():
     assert set(L._SIGS) == set(_header_symbols())
 
 
+def test_tuning_slot_table(monkeypatch):
+    """The MG_TUNE_* table of the public header: unique names, numbers exactly 0 .. 30 with COUNT = 31 (the numbers are
+    ABI: MOEGAN_TUNE specs name them), the binding's TUNE map = the table without the prefix, COUNT and the two retired
+    entries, and ops.tuning refuses an unknown name before it touches the library."""
+    from moegan_mi import _lib as L
+    from moegan_mi import ops
+    txt = re.sub(r"/\*.*?\*/", "", open(os.path.join(REPO, "include", "moegan_hip.h")).read(), flags=re.S)
+    body = re.search(r"enum\s*\{([^}]*MG_TUNE_[^}]*)\}", txt).group(1)
+    entries = [e.strip() for e in body.split(",") if e.strip()]
+    pairs = [re.fullmatch(r"MG_TUNE_(\w+)\s*=\s*(\d+)", e) for e in entries]
+    assert all(pairs), entries  # one entry per slot, each with an explicit number
+    names, numbers = [m.group(1) for m in pairs], [int(m.group(2)) for m in pairs]
+    assert len(set(names)) == len(names)
+    assert names[-1] == "COUNT" and numbers == list(range(32))
+    table = dict(zip(names[:-1], numbers[:-1]))
+    retired = {n for n in table if n.startswith("RETIRED_")}
+    assert retired == {"RETIRED_8", "RETIRED_23"} and table["RETIRED_8"] == 8 and table["RETIRED_23"] == 23
+    assert L.TUNE == {n: v for n, v in table.items() if n not in retired}
+
+    def no_library():
+        raise AssertionError("ops.tuning loaded the library for an unknown slot name")
+    monkeypatch.setattr(L, "lib", no_library)
+    with pytest.raises(L.MGError, match="NO_SUCH"):
+        with ops.tuning(NO_SUCH=1):
+            pass
+    with pytest.raises(L.MGError, match="RETIRED_8"):  # retired slots have no name to override by
+        with ops.tuning(RETIRED_8=1):
+            pass
+
+
 def _f9():
     with open(os.path.join(GOLD, "F9_layout.json")) as f:
         return json.load(f)

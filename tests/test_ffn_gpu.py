@@ -77,43 +77,39 @@ def test_fused_ffn_backward_matches_grouped_gemms(T, E, k, skew, C, occ):
     """Fused expert backward (mg_moe_ffn_bwd, t2i_moe_gan.py:257-263 backward) against the unfused path of
     engine_g.moe_bwd: gP = gG W2_e with the GELU' epilogue and gX = gP W1_e (mg_gemm_grouped) bit-identical; the
     bias gradient against mg_grouped_colsum of the same gP (fp32 summation order) and against float64 sums; C = 128
-    and 256 (the 16x16 / 8x8 blocks), both occupancy forms (tuning slot 14), empty experts, ragged last tiles, the C5
-    routing (E=32 top-4)."""
+    and 256 (the 16x16 / 8x8 blocks), both occupancy forms (tuning slot 14, FFN_BWD_OCC), empty experts, ragged last
+    tiles, the C5 routing (E=32 top-4)."""
     Hd = 4 * C
-    L.call("mg_set_tuning", 14, occ)
-    tok, W1, b1, W2, b2, topi, gate = _case(T, C, E, k, T * 3 + E, empty_expert=skew)
-    row_off, tile_off, perm, pos_of, gate_pos = ops.moe_dispatch(topi, gate, E)
-    n = T * k
-    max_tiles = (n + 127) // 128 + E
-    g = torch.Generator(device=DEV).manual_seed(T + 1)
-    gG = torch.randn(n, C, device=DEV, generator=g).to(bf)
-    Pre = torch.randn(n, Hd, device=DEV, generator=g).to(bf)
-    gP_r = torch.empty(n, Hd, device=DEV, dtype=bf)
-    ops.gemm_grouped(gG, W2.view(-1), row_off, tile_off, max_tiles, Hd, C, b_kc=False, b_gstride=C * Hd, out=gP_r,
-                     ldb=Hd, ep=ops.E(act=L.ACT_MUL_GELU_GRAD, aux=Pre, ld_aux=Hd))
-    gX_r = torch.empty(n, C, device=DEV, dtype=bf)
-    ops.gemm_grouped(gP_r, W1.view(-1), row_off, tile_off, max_tiles, C, Hd, b_kc=False, b_gstride=Hd * C, out=gX_r,
-                     ldb=C)
-    gb1_r = torch.full((E * Hd,), 0.25, device=DEV)
-    ops.grouped_colsum(gP_r, row_off, Hd, n, gb1_r)
-    gP = torch.empty(n, Hd, device=DEV, dtype=bf)
-    gX = torch.empty(n, C, device=DEV, dtype=bf)
-    gb1 = torch.full((E, Hd), 0.25, device=DEV)
-    gb2 = torch.full((E, C), -0.5, device=DEV)
-    Hid = torch.empty(n, Hd, device=DEV, dtype=bf)
-    ops.moe_ffn_bwd(gG, Pre, W1, W2, row_off, tile_off, max_tiles, gP, gX, gb1, gb2, hid=Hid)
-    # GELU(Pre) out of the backward = the GELU the W2 weight gradient forms on load: the two weight gradients are
-    # bit-identical (deterministic mode: one writer per element, same MFMA inputs and order)
-    L.call("mg_set_tuning", 11, 1)
-    try:
-        gw_load = ops.gemm_grouped_wgrad(gG, Pre, row_off, n, C, Hd, torch.zeros(E, C, Hd, device=DEV), b_gelu=1)
-        gw_hid = ops.gemm_grouped_wgrad(gG, Hid, row_off, n, C, Hd, torch.zeros(E, C, Hd, device=DEV))
-    finally:
-        L.call("mg_set_tuning", 11, 0)
-    gb2_r = torch.full((E * C,), -0.5, device=DEV)
-    ops.grouped_colsum(gG, row_off, C, n, gb2_r)
-    torch.cuda.synchronize()
-    L.call("mg_set_tuning", 14, 0)
+    with ops.tuning(FFN_BWD_OCC=occ):
+        tok, W1, b1, W2, b2, topi, gate = _case(T, C, E, k, T * 3 + E, empty_expert=skew)
+        row_off, tile_off, perm, pos_of, gate_pos = ops.moe_dispatch(topi, gate, E)
+        n = T * k
+        max_tiles = (n + 127) // 128 + E
+        g = torch.Generator(device=DEV).manual_seed(T + 1)
+        gG = torch.randn(n, C, device=DEV, generator=g).to(bf)
+        Pre = torch.randn(n, Hd, device=DEV, generator=g).to(bf)
+        gP_r = torch.empty(n, Hd, device=DEV, dtype=bf)
+        ops.gemm_grouped(gG, W2.view(-1), row_off, tile_off, max_tiles, Hd, C, b_kc=False, b_gstride=C * Hd, out=gP_r,
+                         ldb=Hd, ep=ops.E(act=L.ACT_MUL_GELU_GRAD, aux=Pre, ld_aux=Hd))
+        gX_r = torch.empty(n, C, device=DEV, dtype=bf)
+        ops.gemm_grouped(gP_r, W1.view(-1), row_off, tile_off, max_tiles, C, Hd, b_kc=False, b_gstride=Hd * C, out=gX_r,
+                         ldb=C)
+        gb1_r = torch.full((E * Hd,), 0.25, device=DEV)
+        ops.grouped_colsum(gP_r, row_off, Hd, n, gb1_r)
+        gP = torch.empty(n, Hd, device=DEV, dtype=bf)
+        gX = torch.empty(n, C, device=DEV, dtype=bf)
+        gb1 = torch.full((E, Hd), 0.25, device=DEV)
+        gb2 = torch.full((E, C), -0.5, device=DEV)
+        Hid = torch.empty(n, Hd, device=DEV, dtype=bf)
+        ops.moe_ffn_bwd(gG, Pre, W1, W2, row_off, tile_off, max_tiles, gP, gX, gb1, gb2, hid=Hid)
+        # GELU(Pre) out of the backward = the GELU the W2 weight gradient forms on load: the two weight gradients are
+        # bit-identical (deterministic mode: one writer per element, same MFMA inputs and order)
+        with ops.tuning(DETERMINISTIC=1):
+            gw_load = ops.gemm_grouped_wgrad(gG, Pre, row_off, n, C, Hd, torch.zeros(E, C, Hd, device=DEV), b_gelu=1)
+            gw_hid = ops.gemm_grouped_wgrad(gG, Hid, row_off, n, C, Hd, torch.zeros(E, C, Hd, device=DEV))
+        gb2_r = torch.full((E * C,), -0.5, device=DEV)
+        ops.grouped_colsum(gG, row_off, C, n, gb2_r)
+        torch.cuda.synchronize()
     assert torch.equal(gP, gP_r)
     assert torch.equal(gX, gX_r)
     assert torch.equal(gw_hid, gw_load)
@@ -142,10 +138,10 @@ def test_fused_ffn_backward_matches_grouped_gemms(T, E, k, skew, C, occ):
 @pytest.mark.parametrize("T,C,E,k", [(16384, 256, 8, 2), (4096, 512, 8, 2), (1000, 128, 8, 2), (77, 256, 4, 1)])
 def test_grouped_64x64_subtiles_bit_identical(T, C, E, k):
     """Grouped expert GEMMs on 64x64 tiles over the dispatch's 128-row tile table (two sub-tiles per table tile,
-    Grouping.sub_shift; tuning slot 3 = 64, and the automatic choice) equal the 128^2-tile launch bit for bit: the same MFMA k order per
-    output element.  Layer 1 with the bias + GELU + saved pre-activation epilogue, layer 2, and the data gradient
-    (MC weight operand); skewed / empty experts and ragged last tiles (rows past a group's end in the second
-    sub-tile)."""
+    Grouping.sub_shift; tuning slot 3, GEMM_TILE = 64, and the automatic choice) equal the 128^2-tile launch bit for
+    bit: the same MFMA k order per output element.  Layer 1 with the bias + GELU + saved pre-activation epilogue,
+    layer 2, and the data gradient (MC weight operand); skewed / empty experts and ragged last tiles (rows past a
+    group's end in the second sub-tile)."""
     tok, W1, b1, W2, b2, topi, gate = _case(T, C, E, k, 7 * T + C, empty_expert=(T == 1000))
     Hd = 4 * C
     row_off, tile_off, perm, pos_of, gate_pos = ops.moe_dispatch(topi, gate, E)
@@ -166,15 +162,12 @@ def test_grouped_64x64_subtiles_bit_identical(T, C, E, k):
                          ldb=C)
         torch.cuda.synchronize()
         return Pre, Hid, Y, gX
-    L.call("mg_set_tuning", 3, 128)  # 128^2 tiles everywhere
-    try:
+    with ops.tuning(GEMM_TILE=128):  # 128^2 tiles everywhere
         ref = run()
-        L.call("mg_set_tuning", 3, 64)  # 64^2 sub-tiles everywhere
+    with ops.tuning(GEMM_TILE=64):  # 64^2 sub-tiles everywhere
         got = run()
-        L.call("mg_set_tuning", 3, 0)  # the automatic choice (64^2 for K <= 512)
+    with ops.tuning(GEMM_TILE=0):  # the automatic choice (64^2 for K <= 512)
         auto = run()
-    finally:
-        L.call("mg_set_tuning", 3, 0)
     for a, b in zip(auto, ref):
         assert torch.equal(a, b)
     for a, b in zip(got, ref):

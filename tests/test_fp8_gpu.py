@@ -72,11 +72,8 @@ def test_conv_mx8_exact_vs_dequantized(B, H, Cin, Cout, tile):
     wp = pack(Wt).bfloat16()
     wq, wsc = ops.quant_mx8(wp)
     xq, xsc = ops.quant_mx8(x.view(-1, Cin))
-    L.call("mg_set_tuning", 2, tile)
-    try:
+    with ops.tuning(CONV_TILE=tile):
         y = ops.conv2d_mx8(xq.view(B, H, H, Cin), xsc, wq, wsc, Cout, 3, 3, 1, 1, out_dtype=torch.float32)
-    finally:
-        L.call("mg_set_tuning", 2, 0)
     torch.cuda.synchronize()
     xd = deq(xq, xsc).view(B, H, H, Cin).permute(0, 3, 1, 2)
     wd = deq(wq, wsc).view(Cout, 3, 3, Cin).permute(0, 3, 1, 2)

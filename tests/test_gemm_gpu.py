@@ -153,28 +153,24 @@ def test_grouped_gelu_grad_epilogue(C, H4):
 @pytest.mark.parametrize("split", [0, 512, 64])
 def test_gemm_batch_matches_individual(dtype, tol, a_kc, b_kc, split):
     """mg_gemm_batch: 11 problems of different shapes / epilogues (two launches) == plain GEMMs; split 0 = one K
-    pass per tile (default), 512 = split-K slabs at a 512-block target (tuning slot 21), 64 = a 64-block target
-    (no split: the batch has more tiles); "x3" = fp32 operands through split-bf16 products."""
+    pass per tile (default), 512 = split-K slabs at a 512-block target (tuning slot 21, BATCH_SPLIT), 64 = a 64-block
+    target (no split: the batch has more tiles); "x3" = fp32 operands through split-bf16 products."""
     x3 = dtype == "x3"
     if x3:
         dtype = torch.float32
-    L.call("mg_set_tuning", 21, split)
-    prev = ops.set_f32x3(x3)
-    try:
-        _gemm_batch_case(dtype, tol, a_kc, b_kc)
-    finally:
-        ops.set_f32x3(prev)
-        L.call("mg_set_tuning", 21, 0)
+    with ops.tuning(BATCH_SPLIT=split):
+        prev = ops.set_f32x3(x3)
+        try:
+            _gemm_batch_case(dtype, tol, a_kc, b_kc)
+        finally:
+            ops.set_f32x3(prev)
 
 
 def test_gemm_batch_split_atomic():
     """Split-K slabs under atomic epilogues: three problems accumulate into one fp32 output (the value chain's
     shared text-sequence gradient) and one into its own, each slab sum added once."""
-    L.call("mg_set_tuning", 21, 512)
-    try:
+    with ops.tuning(BATCH_SPLIT=512):
         _split_atomic_case()
-    finally:
-        L.call("mg_set_tuning", 21, 0)
 
 
 def _split_atomic_case():
@@ -231,7 +227,8 @@ def _gemm_batch_case(dtype, tol, a_kc, b_kc):
         assert rel(q["out"], r) < tol, (q["M"], q["N"], q["K"])
 
 
-# tuning slots (mg_common.h): 0 = conv weight-gradient tile, 2 = conv forward tile, 3 = plain GEMM tile
+# tuning slots (include/moegan_hip.h): WGRAD_TILE (0) = conv weight-gradient tile, CONV_TILE (2) = conv forward tile,
+# GEMM_TILE (3) = plain GEMM tile
 @pytest.mark.parametrize("tile", [128, 256, 257])
 @pytest.mark.parametrize("B,H,Cin,Cout,k,stride,pad", [(3, 8, 64, 96, 3, 1, 1), (4, 32, 128, 256, 4, 2, 1),
                                                        (2, 8, 256, 512, 3, 1, 1)])
@@ -250,16 +247,11 @@ def test_conv_wide_tiles_bf16(tile, B, H, Cin, Cout, k, stride, pad, scaled):
     xr = xs.clone().requires_grad_(True)
     wr = w.clone().requires_grad_(True)
     (F.conv2d(xr, wr, stride=stride, padding=pad) * gy).sum().backward()
-    try:
-        L.call("mg_set_tuning", 0, tile)
-        L.call("mg_set_tuning", 2, tile)
+    with ops.tuning(WGRAD_TILE=tile, CONV_TILE=tile):
         y = ops.conv2d(xn, wp, Cout, k, k, stride, pad, in_scale=s, out_dtype=torch.float32)
         gw = torch.zeros_like(w)
         ops.conv2d_wgrad(gy.permute(0, 2, 3, 1).contiguous().bfloat16(), xn, Cout, k, k, stride, pad, gw, in_scale=s)
         torch.cuda.synchronize()
-    finally:
-        L.call("mg_set_tuning", 0, 0)
-        L.call("mg_set_tuning", 2, 0)
     assert rel(y.permute(0, 3, 1, 2), ref) < 2e-2
     assert rel(gw, wr.grad) < 4e-2
 
@@ -273,12 +265,9 @@ def test_gemm_wide_tile_bf16(a_kc, b_kc, M, N, K):
     ref = A.float() @ Bm.float().T
     Aa = A if a_kc else A.T.contiguous()
     Bb = Bm if b_kc else Bm.T.contiguous()
-    try:
-        L.call("mg_set_tuning", 3, 257)
+    with ops.tuning(GEMM_TILE=257):
         C = ops.gemm(Aa, Bb, M, N, K, a_kc=a_kc, b_kc=b_kc, out_dtype=torch.float32)
         torch.cuda.synchronize()
-    finally:
-        L.call("mg_set_tuning", 3, 0)
     assert rel(C, ref) < 1e-2
 
 
@@ -350,21 +339,17 @@ def test_conv_narrow_output(dtype, tol, Cout):
 def test_conv_wgrad_stride1_loader(dtype, B, H, Cin, Cout, k):
     """Weight gradients of stride-1 "same" convolutions (the generator's modulated 3x3 / 1x1 convs and MTM offset
     heads, t2i_moe_gan.py:169-180) through the cheap-address column loader (LdMCConvS1): bit-identical to the
-    generic implicit-conv loader (MG_TUNE_S1_OFF = 12 switches it back: same values, same summation order), and
+    generic implicit-conv loader (slot 12, S1_OFF = 1 switches it back: same values, same summation order), and
     equal to the torch reference within the dtype's tolerance."""
-    from moegan_mi import _lib as L
     g = torch.Generator(device=DEV).manual_seed(B * H + Cin)
     x = torch.randn(B, H, H, Cin, device=DEV, generator=g).to(dtype)
     gy = torch.randn(B, H, H, Cout, device=DEV, generator=g).to(dtype)
     pad = k // 2
     gw1 = torch.zeros(Cout, Cin, k, k, device=DEV)
     ops.conv2d_wgrad(gy, x, Cout, k, k, 1, pad, gw1)
-    L.call("mg_set_tuning", 12, 1)
-    try:
+    with ops.tuning(S1_OFF=1):
         gw0 = torch.zeros(Cout, Cin, k, k, device=DEV)
         ops.conv2d_wgrad(gy, x, Cout, k, k, 1, pad, gw0)
-    finally:
-        L.call("mg_set_tuning", 12, 0)
     torch.cuda.synchronize()
     xr = x.float().permute(0, 3, 1, 2).contiguous()
     wr = torch.zeros(Cout, Cin, k, k, device=DEV, requires_grad=True)
@@ -381,8 +366,8 @@ def test_conv_wgrad_stride1_loader(dtype, B, H, Cin, Cout, k):
                                          (128, 256, 65536, 1.0), (512, 512, 2048, 1.0), (8, 128, 3000, 2.0)])
 def test_wide_weight_gradient(M, N, K, alpha):
     """Linear-layer weight gradients C += alpha * A^T B (bf16 [K][M] x [K][N], fp32 C through an atomic epilogue):
-    the long-reduction kernel (csrc/mg_wgrad_wide.hip, forced onto every eligible shape: tuning slot 15 = 2, and on
-    256^2 tiles: 4) against
+    the long-reduction kernel (csrc/mg_wgrad_wide.hip, forced onto every eligible shape: tuning slot 15, WIDE_WGRAD = 2,
+    and on 256^2 tiles: 4) against
     fp64 on the same bf16 operands and against the generic split-K GEMM (slot 15 = 1); fixed-order fold: two calls
     give the same bits.  The automatic routing (slot 15 = 0) is held to the same fp64 bound."""
     g = torch.Generator(device=DEV).manual_seed(M + N + K)
@@ -395,15 +380,12 @@ def test_wide_weight_gradient(M, N, K, alpha):
         ops.gemm(A, B, M, N, K, a_kc=False, b_kc=False, out=C, ep=ops.E(alpha=alpha, atomic=1), splits=0)
         return C
     C4 = run()
-    L.call("mg_set_tuning", 15, 2)
-    try:
+    with ops.tuning(WIDE_WGRAD=2):
         C1, C2 = run(), run()
-        L.call("mg_set_tuning", 15, 4)  # 256^2 tiles where M, N >= 256
+    with ops.tuning(WIDE_WGRAD=4):  # 256^2 tiles where M, N >= 256
         C5 = run()
-        L.call("mg_set_tuning", 15, 1)
+    with ops.tuning(WIDE_WGRAD=1):
         C3 = run()
-    finally:
-        L.call("mg_set_tuning", 15, 0)
     torch.cuda.synchronize()
     scale = float(ref.abs().max())
     assert float((C1.double() - ref).abs().max()) <= 2e-6 * scale * (K / 4096) ** 0.5 + 1e-6
@@ -418,7 +400,7 @@ def test_conv1x1_weight_gradient_long_reduction(B, H, Cin, Cout):
     """1x1 / stride-1 conv weight gradients (ConvolutionBlock.skip_proj, AttentionBlock.proj_in / proj_out,
     t2i_moe_gan.py:574, :615-616) go through the long-reduction kernel (mg_wgrad_wide.hip) when it takes the shape:
     gw += gy^T x over the B*H*W pixels, against fp64 on the same bf16 operands and against the generic conv weight
-    gradient (tuning slot 15 = 1), accumulating into a non-zero gradient."""
+    gradient (tuning slot 15, WIDE_WGRAD = 1), accumulating into a non-zero gradient."""
     g = torch.Generator(device=DEV).manual_seed(B * H + Cin)
     x = torch.randn(B, H, H, Cin, device=DEV, generator=g).bfloat16()
     gy = torch.randn(B, H, H, Cout, device=DEV, generator=g).bfloat16()
@@ -430,11 +412,8 @@ def test_conv1x1_weight_gradient_long_reduction(B, H, Cin, Cout):
         ops.conv2d_wgrad(gy, x, Cout, 1, 1, 1, 0, gw)
         return gw
     gw_auto = run()
-    L.call("mg_set_tuning", 15, 1)
-    try:
+    with ops.tuning(WIDE_WGRAD=1):
         gw_gen = run()
-    finally:
-        L.call("mg_set_tuning", 15, 0)
     torch.cuda.synchronize()
     scale = float((ref - base.double()).abs().max())
     P = B * H * H

@@ -19,15 +19,16 @@ the unfused kernel) and 128; rows = 32 and 128; k = 1 and 3; plain and accumulat
 bf16 operands, fp32 from fp32 operands (the parity mode).  Styles and style gradients are column slices of pitch
 3 Cin + 8, gx a column slice of a sentinel-filled buffer.  At these sizes the library would run several of the plain
 data gradients as split-K slabs, which the fused form leaves to the two kernels; the fused cases therefore run with
-split-K slabs off (tuning slot 5), and test_default_dispatch_and_refused_shapes runs the default dispatch.  Which
-path a case must take is written down in ``expect_fused`` and asserted, so a silent fall-back cannot pass for the
+split-K slabs off (tuning slot 5, NO_SLABS), and test_default_dispatch_and_refused_shapes runs the default dispatch.
+Which path a case must take is written down in ``expect_fused`` and asserted, so a silent fall-back cannot pass for the
 fused kernel.  The dispatch picks the 128^2 and 128 x 256 tiles from 480 tiles on, far beyond a test-sized shape:
-test_fused_large_tiles_against_fp64 forces them with the tile tuning slots (3 for the GEMM, 2 for the conv).
+test_fused_large_tiles_against_fp64 forces them with the tile tuning slots (3, GEMM_TILE, for the GEMM; 2, CONV_TILE,
+for the conv).
 
 A case the fused form refuses runs today's two kernels; from bf16 operands those round gxt to bf16 in between, so
-such a case (and every case in deterministic mode or with tuning slot 29 set) is compared bit for bit with the
-explicit two-kernel sequence, which tests/test_glue_modconv_gpu.py pins to fp64 -- gs to the summation bound where
-mg_modconv_bwd_in itself splits an image over grid.z with atomics (HW = 256 at Cin = 128)."""
+such a case (and every case in deterministic mode or with tuning slot 29, MODGRAD_UNFUSED, set) is compared bit for bit
+with the explicit two-kernel sequence, which tests/test_glue_modconv_gpu.py pins to fp64 -- gs to the summation bound
+where mg_modconv_bwd_in itself splits an image over grid.z with atomics (HW = 256 at Cin = 128)."""
 import pytest
 import torch
 import torch.nn.functional as F
@@ -41,7 +42,6 @@ DEV = "cuda"
 F32, BF16 = torch.float32, torch.bfloat16
 SENT = 7.0
 PAD = 8
-TUNE_NO_SLABS = 5  # mg_common.h MG_TUNE_NO_SLABS
 SHAPES = [(3, 4, 4), (3, 8, 8), (1, 16, 16)]  # (B, H, W)
 CINS = [24, 128]
 ROWS = [32, 128]
@@ -54,11 +54,8 @@ def rnd(t, dtype):
 
 @pytest.fixture
 def no_slabs():
-    L.call("mg_set_tuning", TUNE_NO_SLABS, 1)
-    try:
+    with ops.tuning(NO_SLABS=1):
         yield
-    finally:
-        L.call("mg_set_tuning", TUNE_NO_SLABS, 0)
 
 
 def expect_fused(cdt, k, rows):
@@ -223,12 +220,10 @@ def test_fused_against_fp64(no_slabs, cdt, k, shape):
 @pytest.mark.parametrize("cdt", [BF16, F32], ids=["bf16", "f32"])
 def test_fused_large_tiles_against_fp64(no_slabs, cdt, k, tile):
     """The 128 x 128 and 128 x 256 tiles, which the dispatch picks from 480 tiles on, forced at the test shapes (tuning
-    slots 3 / 2, as for the plain GEMM / conv): a 128-row tile then holds all three 4x4 images and an 80-row tail,
-    two 8x8 images and a half, or half of the 16x16 one; each wave tile (64 rows) spans up to four images.  fp32
-    operands have no 128 x 256 tile (the 128 x 128 one runs again)."""
-    slot = 3 if k == 1 else 2  # mg_common.h MG_TUNE_GEMM_TILE / MG_TUNE_CONV_TILE
-    L.call("mg_set_tuning", slot, tile)
-    try:
+    slots 3 / 2, GEMM_TILE / CONV_TILE, as for the plain GEMM / conv): a 128-row tile then holds all three 4x4 images
+    and an 80-row tail, two 8x8 images and a half, or half of the 16x16 one; each wave tile (64 rows) spans up to four
+    images.  fp32 operands have no 128 x 256 tile (the 128 x 128 one runs again)."""
+    with ops.tuning(**{"GEMM_TILE" if k == 1 else "CONV_TILE": tile}):
         for si, (B, H, W) in enumerate(SHAPES):
             for vi, (odt, Cin, rows, acc) in enumerate(variants(cdt)):
                 if rows != 128 or (vi + si) % 2:
@@ -237,8 +232,6 @@ def test_fused_large_tiles_against_fp64(no_slabs, cdt, k, tile):
                 fused, gx, buf, Gd = c.run()
                 assert fused, c.tag() + f": tile {tile} did not run fused"
                 c.check_fused(gx, buf, Gd)
-    finally:
-        L.call("mg_set_tuning", slot, 0)
 
 
 @pytest.mark.parametrize("Cin", [1024, 2048], ids=["128x128", "128x256"])
@@ -264,12 +257,9 @@ def test_fused_default_large_tiles(k, Cin):
 @pytest.mark.parametrize("k", [1, 3])
 @pytest.mark.parametrize("cdt", [BF16, F32], ids=["bf16", "f32"])
 def test_unfused_modes_are_todays_two_kernels(no_slabs, cdt, k, mode):
-    """Deterministic mode and tuning slot 29 must run exactly the data gradient + mg_modconv_bwd_in pair."""
-    if mode == "deterministic":
-        ops.set_deterministic(True)
-    else:
-        L.call("mg_set_tuning", ops.TUNE_MODGRAD_UNFUSED, 1)
-    try:
+    """Deterministic mode and tuning slot 29 (MODGRAD_UNFUSED) must run exactly the data gradient + mg_modconv_bwd_in
+    pair."""
+    with ops.tuning(**{"DETERMINISTIC" if mode == "deterministic" else "MODGRAD_UNFUSED": 1}):
         for si, (B, H, W) in enumerate(SHAPES):
             for vi, (odt, Cin, rows, acc) in enumerate(variants(cdt)):
                 if (vi + si) % 2:  # half of the variants per shape: every Cin / rows / dtype on every shape pair
@@ -279,9 +269,6 @@ def test_unfused_modes_are_todays_two_kernels(no_slabs, cdt, k, mode):
                 assert not fused, c.tag() + " ran fused in " + mode
                 c.check_same_as_two_kernels(gx, buf, Gd,
                                             exact_gs=mode == "deterministic" or H * W <= 64 or Cin < 128)
-    finally:
-        ops.set_deterministic(False)
-        L.call("mg_set_tuning", ops.TUNE_MODGRAD_UNFUSED, 0)
 
 
 @pytest.mark.parametrize("cdt", [BF16, F32], ids=["bf16", "f32"])
@@ -304,18 +291,16 @@ def test_default_dispatch_and_refused_shapes(cdt):
 
 
 def test_entry_points_refuse_what_the_predicate_refuses():
-    """mg_gemm with mg_epilogue.gs set while mg_modconv_dgrad_fusable says no (here: tuning slot 29) is an argument
-    error, never a silent plain GEMM; with the slot cleared the same call is admitted."""
+    """mg_gemm with mg_epilogue.gs set while mg_modconv_dgrad_fusable says no (here: tuning slot 29,
+    MODGRAD_UNFUSED) is an argument error, never a silent plain GEMM; with the slot cleared the same call is
+    admitted."""
     c = Case(BF16, BF16, 1, 3, 4, 4, 24, 32, 0, seed=5)
     gx, buf, Gd = c.outputs()
     args = (c.gyt_d, c.w_d, 1, 3, 4, 4, 24, c.x_d, c.Sd[:, c.sl], gx, Gd[:, c.sl], 0)
-    L.call("mg_set_tuning", ops.TUNE_MODGRAD_UNFUSED, 1)
-    try:
+    with ops.tuning(MODGRAD_UNFUSED=1):
         assert not ops.modconv_dgrad_fusable(c.gyt_d, 1, 3, 4, 4, 24, c.x_d, c.Sd[:, c.sl], gx)
         with pytest.raises(L.MGError, match=r"\(-1\)"):
             ops.modconv_dgrad(*args)
-    finally:
-        L.call("mg_set_tuning", ops.TUNE_MODGRAD_UNFUSED, 0)
     assert ops.modconv_dgrad_fusable(c.gyt_d, 1, 3, 4, 4, 24, c.x_d, c.Sd[:, c.sl], gx)
     ops.modconv_dgrad(*args)
     torch.cuda.synchronize()

@@ -1,8 +1,8 @@
 """One C2-shaped training step (bf16, E = 8 top-2, B = 4) with the modulated conv's gx / gs in the data-gradient
-GEMM's epilogue (the default) and one with tuning slot 29 set (today's data gradient + mg_modconv_bwd_in): same
-seeded weights, inputs and router noise.  The fused epilogue forms the same fp32 gxt and gives it the rounding the
-gxt buffer gave it, so the two steps differ in the order of fp32 sums (the style gradients' atomics) and in how the
-compiler contracts the accumulating store's multiply-add, nothing else.
+GEMM's epilogue (the default) and one with tuning slot 29, MODGRAD_UNFUSED, set (today's data gradient +
+mg_modconv_bwd_in): same seeded weights, inputs and router noise.  The fused epilogue forms the same fp32 gxt and gives
+it the rounding the gxt buffer gave it, so the two steps differ in the order of fp32 sums (the style gradients' atomics)
+and in how the compiler contracts the accumulating store's multiply-add, nothing else.
 
 Bar: the clipped gradient vectors of the two steps (g_grad, d_grad as handed to AdamW) agree within the step's bf16
 floor, the yardstick of tests/test_step_bf16_gpu.py built from tests/steputil.py: the relative L2 distance between
@@ -36,13 +36,11 @@ def _clipped(out):
 
 
 def _device_step(inputs, unfused, slopes=None):
-    from moegan_mi import _lib as L
     from moegan_mi import ops
     real, text, z, eps_d, eps_g, perm = inputs
     cu = lambda t: t.to(DEV)  # noqa: E731
     ts = gpu_step(E, TOPK, "bf16", DEV)
-    L.call("mg_set_tuning", ops.TUNE_MODGRAD_UNFUSED, 1 if unfused else 0)
-    try:
+    with ops.tuning(MODGRAD_UNFUSED=1 if unfused else 0):
         args = (cu(real), cu(text), cu(z), [tuple(map(cu, e)) for e in eps_d], [tuple(map(cu, e)) for e in eps_g],
                 cu(perm.int()))
         kw = dict(anneal=3.0, lr_g=LR, lr_d=LR, eff_kl_weight=EFF_KL)
@@ -52,8 +50,6 @@ def _device_step(inputs, unfused, slopes=None):
         else:
             out = ts.step(*args, **kw)
         torch.cuda.synchronize()
-    finally:
-        L.call("mg_set_tuning", ops.TUNE_MODGRAD_UNFUSED, 0)
     assert int(out["flags"][0]) == 0
     return ts, out
 

@@ -2,9 +2,9 @@
 t2i_moe_gan.py:199-216, and its backward) on the direct halo-tile kernels of csrc/mg_narrow.hip, routed from
 mg_conv2d_fwd / mg_conv2d_wgrad for 4x4 .. 16x16 maps, against
 
-  * the implicit-GEMM path they replace (tuning slot 16 = 1): the same products summed in another order (channel
-    chunks outermost, split slabs on the small maps), so fp32 results agree to summation noise and bf16 results to
-    one rounding;
+  * the implicit-GEMM path they replace (tuning slot 16, NARROW = 1): the same products summed in another order
+    (channel chunks outermost, split slabs on the small maps), so fp32 results agree to summation noise and bf16
+    results to one rounding;
   * plain fp32 / fp64 PyTorch convolutions on the same bf16 operands.
 
 Cases: the three map sizes the offset heads run at, Cin 128 / 256 / 512, a batch that leaves the last 128-pixel
@@ -20,41 +20,32 @@ DEV = "cuda"
 bf = torch.bfloat16
 
 
-def _set(v):
-    from moegan_mi import _lib as L
-    L.call("mg_set_tuning", 16, v)
-
-
 @pytest.mark.parametrize("wpx", [0, 4])
 @pytest.mark.parametrize("B,S,Cin,out_dtype", [(8, 16, 256, bf), (3, 16, 128, torch.float32), (6, 8, 512, bf),
                                                (5, 8, 256, bf), (9, 4, 512, bf), (2, 4, 128, torch.float32)])
 def test_offset_head_forward(B, S, Cin, out_dtype, wpx):
-    """``wpx``: tuning slot 19 (0: 128-pixel tiles, 4: 256-pixel tiles with four pixel fragments per wave)."""
+    """``wpx``: tuning slot 19, NARROW_WPX (0: 128-pixel tiles, 4: 256-pixel tiles with four pixel fragments per
+    wave)."""
     from moegan_mi import _lib as L
     from moegan_mi import ops
-    L.call("mg_set_tuning", 19, wpx)
     g = torch.Generator(device=DEV).manual_seed(B * 100 + S + Cin)
     x = (torch.randn(B, S, S, Cin, device=DEV, generator=g)).to(bf)
     W = (torch.randn(32, Cin, 3, 3, device=DEV, generator=g) * (9 * Cin) ** -0.5)
     bias = torch.randn(32, device=DEV, generator=g) * 0.1
     wp = ops.pack_conv(W, bf)
     ep = ops.E(bias=bias, act=L.ACT_LRELU)
-    y = ops.conv2d(x, wp, 32, 3, 3, 1, 1, out_dtype=out_dtype, ep=ep)
-    _set(1)
-    try:
-        y_ref = ops.conv2d(x, wp, 32, 3, 3, 1, 1, out_dtype=out_dtype, ep=ep)
-    finally:
-        _set(0)
-    torch.cuda.synchronize()
+    with ops.tuning(NARROW_WPX=wpx):
+        y = ops.conv2d(x, wp, 32, 3, 3, 1, 1, out_dtype=out_dtype, ep=ep)
+        with ops.tuning(NARROW=1):
+            y_ref = ops.conv2d(x, wp, 32, 3, 3, 1, 1, out_dtype=out_dtype, ep=ep)
+        y2 = ops.conv2d(x, wp, 32, 3, 3, 1, 1, out_dtype=out_dtype, ep=ep)
+        torch.cuda.synchronize()
     t = F.leaky_relu(F.conv2d(x.float().permute(0, 3, 1, 2), W.to(bf).float(), bias, padding=1), 0.2)
     t = t.permute(0, 2, 3, 1)
     scale = float(t.abs().max())
     tol = 2e-5 if out_dtype == torch.float32 else 1e-2
     assert float((y.float() - y_ref.float()).abs().max()) <= tol * scale
     assert float((y.float() - t).abs().max()) <= tol * scale
-    y2 = ops.conv2d(x, wp, 32, 3, 3, 1, 1, out_dtype=out_dtype, ep=ep)
-    torch.cuda.synchronize()
-    L.call("mg_set_tuning", 19, 0)
     assert torch.equal(y, y2)
 
 
@@ -72,11 +63,8 @@ def test_offset_head_data_gradient(B, S, Cout, out_dtype):
     gx = gx0.clone()
     ops.conv2d(ga, wflip, Cout, 3, 3, 1, 1, out=gx, ep=ops.E(accumulate=1))
     gx_ref = gx0.clone()
-    _set(1)
-    try:
+    with ops.tuning(NARROW=1):
         ops.conv2d(ga, wflip, Cout, 3, 3, 1, 1, out=gx_ref, ep=ops.E(accumulate=1))
-    finally:
-        _set(0)
     torch.cuda.synchronize()
     # fp64 autograd of the forward conv on the same bf16 operands
     xx = torch.zeros(B, Cout, S, S, dtype=torch.float64, device=DEV, requires_grad=True)
@@ -100,11 +88,8 @@ def test_offset_head_weight_gradient(B, S, Cin):
         ops.conv2d_wgrad(ga, x, 32, 3, 3, 1, 1, gw)
         return gw
     gw1, gw2 = run(), run()
-    _set(1)
-    try:
+    with ops.tuning(NARROW=1):
         gw_ref = run()
-    finally:
-        _set(0)
     torch.cuda.synchronize()
     w = torch.zeros(32, Cin, 3, 3, dtype=torch.float64, device=DEV, requires_grad=True)
     (F.conv2d(x.permute(0, 3, 1, 2).double(), w, padding=1) * ga.permute(0, 3, 1, 2).double()).sum().backward()

@@ -2,12 +2,12 @@
 defines the tuning slots itself, is built with the host compiler under AddressSanitizer and UBSan, and checks
 
   structure, over M x N x K x (bf16, fp32, split-bf16 fp32) x epilogue forms and a grid of convs, at default tuning
-  and under slots 5 = 1, 3 in {64, 128, 257}, 2 in {64, 128, 256, 257}, 9 = 2 and 11 = 1: every slab plan has
-  splits >= 2 chunks of whole K steps that cover K with none empty, every tile is one the library builds for the
-  dtype, split-bf16 and loader-transform GEMMs stay on 64^2;
-  anchors: the shapes whose measurements are quoted next to the rules take the tile the comment says;
-  the four shapes of test_modconv_fused_gpu.py::test_fused_default_large_tiles come out as one launch on 128^2
-  (twice) and 128 x 256 (twice) -- the GPU test cannot see which tile ran.
+  and under slots NO_SLABS (5) = 1, GEMM_TILE (3) in {64, 128, 257}, CONV_TILE (2) in {64, 128, 256, 257}, SHORTK (9) =
+  2 and DETERMINISTIC (11) = 1: every slab plan has splits >= 2 chunks of whole K steps that cover K with none empty,
+  every tile is one the library builds for the dtype, split-bf16 and loader-transform GEMMs stay on 64^2; anchors: the
+  shapes whose measurements are quoted next to the rules take the tile the comment says; the four shapes of
+  test_modconv_fused_gpu.py::test_fused_default_large_tiles come out as one launch on 128^2 (twice) and 128 x 256
+  (twice) -- the GPU test cannot see which tile ran.
 
 No device and no library build is needed."""
 import os

@@ -57,8 +57,7 @@ def test_router_fwd_across_experts(E, k, dtype):
 def test_router_fwd_mfma_shapes(T, C, E, k, HW):
     """bf16 router logits on the matrix cores (Wfc as bf16 hi + lo): several channel chunks (C = 512), ragged
     token counts, several tiles per wave (T > 65536), C not a multiple of the chunk; against fp64 and against the
-    lane-FMA team kernel (tuning slot 24 = 1)."""
-    from moegan_mi import _lib as L
+    lane-FMA team kernel (tuning slot 24, ROUTER_TEAM = 1)."""
     g = torch.Generator(device=DEV).manual_seed(T + C + E)
     B = (T + HW - 1) // HW
     tok = torch.randn(T, C, device=DEV, generator=g).to(torch.bfloat16)
@@ -66,11 +65,8 @@ def test_router_fwd_mfma_shapes(T, C, E, k, HW):
     Lt = torch.randn(B, E, device=DEV, generator=g)
     temp = torch.tensor([1.1], device=DEV)
     probs, zlog, topi, gate = ops.router_fwd(tok, Wfc, Lt, E, k, HW, temp, 1.0)
-    L.call("mg_set_tuning", 24, 1)
-    try:
+    with ops.tuning(ROUTER_TEAM=1):
         probs_t, zlog_t, topi_t, gate_t = ops.router_fwd(tok, Wfc, Lt, E, k, HW, temp, 1.0)
-    finally:
-        L.call("mg_set_tuning", 24, 0)
     p, z, ti, gt = ref_router(tok.float(), Wfc, Lt, HW, 1.1, 1.0, k)
     assert rel(zlog, z) < 1e-5 and rel(zlog, zlog_t) < 1e-5
     assert rel(probs, p) < 1e-5
@@ -88,8 +84,7 @@ def test_router_fwd_mfma_shapes(T, C, E, k, HW):
 def test_router_bwd_against_autograd(E, k, HW, B):
     """mg_router_bwd (8-lane teams for E >= 8, thread per token for E = 4) against fp64 autograd of the router's
     softmax / clamp / renormalise / top-k gate (t2i_moe_gan.py:375-402): the raw-logit gradient, the per-image
-    sums and the temperature gradient; and against the thread-per-token kernel (tuning slot 24 = 2)."""
-    from moegan_mi import _lib as L
+    sums and the temperature gradient; and against the thread-per-token kernel (tuning slot 24, ROUTER_TEAM = 2)."""
     g = torch.Generator(device=DEV).manual_seed(E * 1000 + HW + B)
     T, C = B * HW, 128
     tok = torch.randn(T, C, device=DEV, generator=g).to(torch.bfloat16)
@@ -111,11 +106,8 @@ def test_router_bwd_against_autograd(E, k, HW, B):
         return g_raw, gsum, gt
 
     g_raw, gsum, gt = run()
-    L.call("mg_set_tuning", 24, 2)
-    try:
+    with ops.tuning(ROUTER_TEAM=2):
         g_raw2, gsum2, gt2 = run()
-    finally:
-        L.call("mg_set_tuning", 24, 0)
     te = min(max(1.3 * 0.9, 0.5), 5.0)
     raw = (zlog.double() * te).requires_grad_(True)
     tp = torch.tensor([1.3], dtype=torch.float64, device=DEV, requires_grad=True)
@@ -160,19 +152,15 @@ def test_token_and_feature_grad_across_experts(E):
 def test_token_grad_mfma_shapes(T, C, E, k, out_dtype):
     """Token gradient with the router term on the matrix cores (both fp32 operands as bf16 hi + lo): one and
     several tiles per block, ragged token counts, E = 8 / 16 (zero k-rows); against fp64 and against the lane-FMA
-    kernel (tuning slot 24 = 4)."""
-    from moegan_mi import _lib as L
+    kernel (tuning slot 24, ROUTER_TEAM = 4)."""
     g = torch.Generator(device=DEV).manual_seed(T + C * 3 + E)
     gX = torch.randn(T * k, C, device=DEV, generator=g).to(torch.bfloat16)
     pos_of = torch.randperm(T * k, device=DEV, generator=g).to(torch.int32)
     g_raw = torch.randn(T, E, device=DEV, generator=g)
     Wfc = torch.randn(C, E, device=DEV, generator=g) * 0.5
     out = ops.moe_token_grad(gX, pos_of, g_raw, Wfc, torch.empty(T, C, device=DEV, dtype=out_dtype), k)
-    L.call("mg_set_tuning", 24, 4)
-    try:
+    with ops.tuning(ROUTER_TEAM=4):
         out_l = ops.moe_token_grad(gX, pos_of, g_raw, Wfc, torch.empty(T, C, device=DEV, dtype=out_dtype), k)
-    finally:
-        L.call("mg_set_tuning", 24, 0)
     ref = gX.double()[pos_of.long().view(T, k)].sum(1) + g_raw.double() @ Wfc.double().T
     tol = 1e-5 if out_dtype == torch.float32 else 8e-3
     assert rel(out, ref) < tol and rel(out_l, ref) < tol

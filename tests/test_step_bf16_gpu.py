@@ -139,9 +139,10 @@ def _deterministic():
 def _device_realization(E, topk, ts, before, inputs, lr):
     """Diagnostic only (reported, never part of a bar): the same device step from the same state with one legitimate
     implementation change -- the MTM offset heads' forward conv on the implicit GEMM instead of the direct halo-tile
-    kernel (tuning slot 16 = 2; their bf16 outputs differ by one rounding in ~0.02 % of elements), the device-side
-    counterpart of the oracle's offset-head sensitivity draws.  Returns the clipped G / D gradient vectors."""
-    from moegan_mi import _lib as L
+    kernel (tuning slot 16, NARROW = 2; their bf16 outputs differ by one rounding in ~0.02 % of elements), the
+    device-side counterpart of the oracle's offset-head sensitivity draws.  Returns the clipped G / D gradient
+    vectors."""
+    from moegan_mi import ops
     ts2 = gpu_step(E, topk, "bf16", DEV)
     for which, st2 in (("G", ts2.gs), ("D", ts2.ds)):
         data, m, v, sd, sdk = before[which]
@@ -152,14 +153,11 @@ def _device_realization(E, topk, ts, before, inputs, lr):
         st2.step_dev_kl.copy_(sdk)
     real, text, z, eps_d, eps_g, perm = inputs
     cu = lambda t: t.to(DEV)  # noqa: E731
-    L.call("mg_set_tuning", 16, 2)
-    try:
+    with ops.tuning(NARROW=2):
         out = ts2.step(cu(real), cu(text), cu(z), [tuple(map(cu, e)) for e in eps_d],
                        [tuple(map(cu, e)) for e in eps_g], cu(perm.int()), anneal=3.0, lr_g=lr, lr_d=lr,
                        eff_kl_weight=EFF_KL)
         torch.cuda.synchronize()
-    finally:
-        L.call("mg_set_tuning", 16, 0)
     res = {}
     for which, key, max_norm in (("D", "d", 0.7), ("G", "g", 0.8)):
         coef = min(1.0, max_norm / (float(out[key + "_grad_sumsq"][0]) ** 0.5 + 1e-6))

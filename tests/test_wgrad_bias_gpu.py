@@ -11,8 +11,8 @@ Column 0 of every gradient holds terms that cancel exactly (+v, -v pairs).
 The weight gradient must not notice the bias output: bit-identical to the plain entry point wherever that path has a
 fixed order (conv slabs + fold, the d0 block partials, one K split of the grouped kernel), within the same kind of
 bound against float64 where the K splits meet in atomics.  Guard words round the bias buffer must survive.  In
-deterministic mode and with tuning slot 30 set the predicates say no, the entry points refuse, and the ops wrappers
-run exactly the plain weight gradient + column sum."""
+deterministic mode and with tuning slot 30 (WGRAD_BIAS_UNFUSED) set the predicates say no, the entry points refuse, and
+the ops wrappers run exactly the plain weight gradient + column sum."""
 import pytest
 import torch
 
@@ -24,23 +24,7 @@ DEV = "cuda"
 F32, BF16 = torch.float32, torch.bfloat16
 SENT = 1234.5
 PAD = 8
-TUNE_WGRAD_TILE, TUNE_GWGRAD_TILE, TUNE_S1_OFF, TUNE_DET, TUNE_UNFUSED = 0, 1, 12, 11, 30
 EPS24, EPS23 = 2.0 ** -24, 2.0 ** -23
-
-
-class tuning:
-    """Set library tuning slots for the duration of a with-block."""
-
-    def __init__(self, **slots):
-        self.slots = {int(k[1:]): v for k, v in slots.items()}
-
-    def __enter__(self):
-        for k, v in self.slots.items():
-            L.call("mg_set_tuning", k, v)
-
-    def __exit__(self, *exc):
-        for k in self.slots:
-            L.call("mg_set_tuning", k, 0)
 
 
 def grad_rows(rows, cols, g):
@@ -114,16 +98,16 @@ CONV_CASES = [
     # (Cin, Cout, k, stride, B, H, tuning)                    P = 4096 output pixels: more than one K split
     (16, 16, 3, 1, 16, 16, {}),                               # 64^2 tile, stride-1 column loader (LDS-DMA images)
     (16, 72, 3, 1, 16, 16, {}),                               # two row tiles, the second ragged
-    (16, 72, 3, 1, 16, 16, {"s12": 1}),                       # generic column loader: register-staged images
-    (16, 128, 3, 1, 16, 16, {"s0": 128}),                     # 128^2 tile
+    (16, 72, 3, 1, 16, 16, {"S1_OFF": 1}),                    # generic column loader: register-staged images
+    (16, 128, 3, 1, 16, 16, {"WGRAD_TILE": 128}),             # 128^2 tile
     (16, 128, 4, 2, 16, 32, {}),                              # 4x4 / stride 2 / pad 1, 64^2, register-staged
-    (16, 128, 4, 2, 16, 32, {"s0": 128}),                     # the same on the 128^2 tile
+    (16, 128, 4, 2, 16, 32, {"WGRAD_TILE": 128}),             # the same on the 128^2 tile
 ]
 
 
 @pytest.mark.parametrize("Cin,Cout,k,stride,B,H,slots", CONV_CASES)
 def test_conv_wgrad_bias(Cin, Cout, k, stride, B, H, slots):
-    with tuning(**slots):
+    with ops.tuning(**slots):
         case = conv_case(Cin, Cout, k, stride, B, H, seed=Cout + k)
         gw_p, *_ = run_conv(case, fused=False)
         gw_f, buf, view, prior, sums, abs_sums, P = run_conv(case, fused=True)
@@ -170,10 +154,10 @@ def run_grouped(M, N, splits, fused, b_gelu=0, seed=5):
     return C, C0.double(), ref, tot, buf, view, prior, sums, abs_sums
 
 
-@pytest.mark.parametrize("M,N,slots", [(128, 136, {}), (72, 40, {}), (128, 136, {"s1": 64})])
+@pytest.mark.parametrize("M,N,slots", [(128, 136, {}), (72, 40, {}), (128, 136, {"GWGRAD_TILE": 64})])
 @pytest.mark.parametrize("splits", [1, 2])
 def test_grouped_wgrad_bias(M, N, slots, splits):
-    with tuning(**slots):
+    with ops.tuning(**slots):
         C_p, *_ = run_grouped(M, N, splits, fused=False)
         C_f, C0, ref, tot, buf, view, prior, sums, abs_sums = run_grouped(M, N, splits, fused=True)
     nmax = max(GROUP_ROWS)
@@ -236,10 +220,10 @@ def test_gemm_wgrad_bias(rows):
 
 
 def test_wide_wgrad_bias():
-    """Tuning slot 15 = 2 puts every eligible shape on the long-reduction kernel: two row tiles (the second ragged,
-    M = 136), K = 2048 + 40 rows (a ragged last K step), fixed-order fold of the partial tiles."""
+    """Tuning slot 15, WIDE_WGRAD = 2, puts every eligible shape on the long-reduction kernel: two row tiles (the second
+    ragged, M = 136), K = 2048 + 40 rows (a ragged last K step), fixed-order fold of the partial tiles."""
     M, N, rows = 136, 128, 2048 + 40
-    with tuning(s15=2):
+    with ops.tuning(WIDE_WGRAD=2):
         C_p, *_ = run_linear(M, N, rows, fused=False)
         C_f, C0, ref, tot, buf, view, prior, sums, abs_sums = run_linear(M, N, rows, fused=True)
     check_bias(buf, view, prior, sums, abs_sums, rows)
@@ -293,11 +277,12 @@ def same_sums(a, b, g2d, prior, exact):
     return bool(((a.double() - b.double()).abs() <= bound).all())
 
 
-@pytest.mark.parametrize("slot", [TUNE_DET, TUNE_UNFUSED])
+@pytest.mark.parametrize("slot", ["DETERMINISTIC", "WGRAD_BIAS_UNFUSED"], ids=["11", "30"])
 def test_refused_modes_run_the_column_sums(slot):
-    """Deterministic mode / slot 30: predicates 0, the *_bias entry points refuse, and ops.* with bias_grad= runs the
-    plain weight gradient followed by the column sum: those calls and no other, and their results."""
-    det = slot == TUNE_DET
+    """Deterministic mode (slot 11) / slot 30, WGRAD_BIAS_UNFUSED: predicates 0, the *_bias entry points refuse, and
+    ops.* with bias_grad= runs the plain weight gradient followed by the column sum: those calls and no other, and
+    their results."""
+    det = slot == "DETERMINISTIC"
     names = []
 
     def hook(name, args, run):
@@ -314,58 +299,58 @@ def test_refused_modes_run_the_column_sums(slot):
     img = (torch.rand(B0, 3, H0, H0, generator=g) * 2 - 1).to(DEV)
     st0 = (3 * H0 * H0, H0, 1, H0 * H0)
     g0 = grad_rows(B0 * 16, 128, g).view(B0, 4, 4, 128).to(DEV)
-    L.call("mg_set_tuning", slot, 1)
-    try:
-        lib = L.lib()
-        assert lib.mg_conv2d_wgrad_bias_fusable(L.MG_BF16, 16, 16, 16, None, Cout, KH, KW, stride, pad) == 0
-        assert lib.mg_gemm_grouped_wgrad_bias_fusable(L.MG_BF16, None) == 0
-        assert lib.mg_d0_wgrad_bias_fusable() == 0
-        b = torch.zeros(Cout, device=DEV)
-        with pytest.raises(L.MGError):
-            L.call("mg_conv2d_wgrad_bias", L.MG_BF16, L.ptr(gy), Cout, L.ptr(x), 16, 16, 16, 16, None, Cout, KH, KW,
-                   stride, pad, L.ptr(gw0.clone()), 0, L.ptr(b), L.stream())
-        # conv
-        gw_a, gw_b = gw0.clone(), gw0.clone()
-        b_a, b_b = torch.full((Cout,), 2.0, device=DEV), torch.full((Cout,), 2.0, device=DEV)
-        L.HOOK = hook
-        ops.conv2d_wgrad(gy, x, Cout, KH, KW, stride, pad, gw_a, bias_grad=b_a)
-        ops.gemm_grouped_wgrad(A, Bm, row_off, 388, 72, 40, torch.ones(4, 72, 40, device=DEV), splits=1,
-                               bias_grad=torch.zeros(4, 72, device=DEV))
-        ops.linear_wgrad(A, Bm, torch.ones(72, 40, device=DEV), bias_grad=torch.zeros(72, device=DEV))
-        ops.d0_wgrad(img, st0, B0, H0, H0, g0, torch.ones(128, 48, device=DEV), bias_grad=torch.zeros(128, device=DEV))
-        L.HOOK = None
-        assert names == ["mg_conv2d_wgrad", "mg_colsum", "mg_gemm_grouped_wgrad", "mg_grouped_colsum", "mg_gemm",
-                         "mg_colsum", "mg_d0_wgrad", "mg_colsum"], names
-        ops.conv2d_wgrad(gy, x, Cout, KH, KW, stride, pad, gw_b)
-        ops.colsum(gy.view(-1, Cout), b_b)
-        assert torch.equal(gw_a, gw_b) and same_sums(b_a, b_b, gy.view(-1, Cout), 2.0, det)
-        # grouped
-        C_a, C_b = torch.ones(4, 72, 40, device=DEV), torch.ones(4, 72, 40, device=DEV)
-        gb_a, gb_b = torch.full((4, 72), 2.0, device=DEV), torch.full((4, 72), 2.0, device=DEV)
-        ops.gemm_grouped_wgrad(A, Bm, row_off, 388, 72, 40, C_a, splits=1, bias_grad=gb_a)
-        ops.gemm_grouped_wgrad(A, Bm, row_off, 388, 72, 40, C_b, splits=1)
-        ops.grouped_colsum(A, row_off, 72, 388, gb_b)
-        assert torch.equal(C_a, C_b)
-        for i in range(4):
-            assert same_sums(gb_a[i], gb_b[i], A[off[i]:off[i + 1]], 2.0, det)
-        # linear layer (388 rows: two K splits)
-        assert lib.mg_gemm_wgrad_bias_fusable(L.MG_BF16) == 0
-        W_a, W_b = torch.ones(72, 40, device=DEV), torch.ones(72, 40, device=DEV)
-        l_a, l_b = torch.full((72,), 2.0, device=DEV), torch.full((72,), 2.0, device=DEV)
-        ops.linear_wgrad(A, Bm, W_a, bias_grad=l_a)
-        ops.linear_wgrad(A, Bm, W_b)
-        ops.colsum(A, l_b)
-        if det:  # (default mode: the two K splits meet in atomics, any order)
-            assert torch.equal(W_a, W_b)
-        assert same_sums(l_a, l_b, A, 2.0, det)
-        # d0
-        dw_a, dw_b = torch.ones(128, 48, device=DEV), torch.ones(128, 48, device=DEV)
-        d_a, d_b = torch.full((128,), 2.0, device=DEV), torch.full((128,), 2.0, device=DEV)
-        ops.d0_wgrad(img, st0, B0, H0, H0, g0, dw_a, bias_grad=d_a)
-        ops.d0_wgrad(img, st0, B0, H0, H0, g0, dw_b)
-        ops.colsum(g0.view(-1, 128), d_b)
-        torch.cuda.synchronize()
-        assert torch.equal(dw_a, dw_b) and same_sums(d_a, d_b, g0.view(-1, 128), 2.0, det)
-    finally:
-        L.HOOK = None
-        L.call("mg_set_tuning", slot, 0)
+    with ops.tuning(**{slot: 1}):
+        try:
+            lib = L.lib()
+            assert lib.mg_conv2d_wgrad_bias_fusable(L.MG_BF16, 16, 16, 16, None, Cout, KH, KW, stride, pad) == 0
+            assert lib.mg_gemm_grouped_wgrad_bias_fusable(L.MG_BF16, None) == 0
+            assert lib.mg_d0_wgrad_bias_fusable() == 0
+            b = torch.zeros(Cout, device=DEV)
+            with pytest.raises(L.MGError):
+                L.call("mg_conv2d_wgrad_bias", L.MG_BF16, L.ptr(gy), Cout, L.ptr(x), 16, 16, 16, 16, None, Cout, KH, KW,
+                       stride, pad, L.ptr(gw0.clone()), 0, L.ptr(b), L.stream())
+            # conv
+            gw_a, gw_b = gw0.clone(), gw0.clone()
+            b_a, b_b = torch.full((Cout,), 2.0, device=DEV), torch.full((Cout,), 2.0, device=DEV)
+            L.HOOK = hook
+            ops.conv2d_wgrad(gy, x, Cout, KH, KW, stride, pad, gw_a, bias_grad=b_a)
+            ops.gemm_grouped_wgrad(A, Bm, row_off, 388, 72, 40, torch.ones(4, 72, 40, device=DEV), splits=1,
+                                   bias_grad=torch.zeros(4, 72, device=DEV))
+            ops.linear_wgrad(A, Bm, torch.ones(72, 40, device=DEV), bias_grad=torch.zeros(72, device=DEV))
+            ops.d0_wgrad(img, st0, B0, H0, H0, g0, torch.ones(128, 48, device=DEV),
+                         bias_grad=torch.zeros(128, device=DEV))
+            L.HOOK = None
+            assert names == ["mg_conv2d_wgrad", "mg_colsum", "mg_gemm_grouped_wgrad", "mg_grouped_colsum", "mg_gemm",
+                             "mg_colsum", "mg_d0_wgrad", "mg_colsum"], names
+            ops.conv2d_wgrad(gy, x, Cout, KH, KW, stride, pad, gw_b)
+            ops.colsum(gy.view(-1, Cout), b_b)
+            assert torch.equal(gw_a, gw_b) and same_sums(b_a, b_b, gy.view(-1, Cout), 2.0, det)
+            # grouped
+            C_a, C_b = torch.ones(4, 72, 40, device=DEV), torch.ones(4, 72, 40, device=DEV)
+            gb_a, gb_b = torch.full((4, 72), 2.0, device=DEV), torch.full((4, 72), 2.0, device=DEV)
+            ops.gemm_grouped_wgrad(A, Bm, row_off, 388, 72, 40, C_a, splits=1, bias_grad=gb_a)
+            ops.gemm_grouped_wgrad(A, Bm, row_off, 388, 72, 40, C_b, splits=1)
+            ops.grouped_colsum(A, row_off, 72, 388, gb_b)
+            assert torch.equal(C_a, C_b)
+            for i in range(4):
+                assert same_sums(gb_a[i], gb_b[i], A[off[i]:off[i + 1]], 2.0, det)
+            # linear layer (388 rows: two K splits)
+            assert lib.mg_gemm_wgrad_bias_fusable(L.MG_BF16) == 0
+            W_a, W_b = torch.ones(72, 40, device=DEV), torch.ones(72, 40, device=DEV)
+            l_a, l_b = torch.full((72,), 2.0, device=DEV), torch.full((72,), 2.0, device=DEV)
+            ops.linear_wgrad(A, Bm, W_a, bias_grad=l_a)
+            ops.linear_wgrad(A, Bm, W_b)
+            ops.colsum(A, l_b)
+            if det:  # (default mode: the two K splits meet in atomics, any order)
+                assert torch.equal(W_a, W_b)
+            assert same_sums(l_a, l_b, A, 2.0, det)
+            # d0
+            dw_a, dw_b = torch.ones(128, 48, device=DEV), torch.ones(128, 48, device=DEV)
+            d_a, d_b = torch.full((128,), 2.0, device=DEV), torch.full((128,), 2.0, device=DEV)
+            ops.d0_wgrad(img, st0, B0, H0, H0, g0, dw_a, bias_grad=d_a)
+            ops.d0_wgrad(img, st0, B0, H0, H0, g0, dw_b)
+            ops.colsum(g0.view(-1, 128), d_b)
+            torch.cuda.synchronize()
+            assert torch.equal(dw_a, dw_b) and same_sums(d_a, d_b, g0.view(-1, 128), 2.0, det)
+        finally:
+            L.HOOK = None

@@ -1,8 +1,8 @@
 """One seeded C2-layout training step (bf16, E = 8 top-2, B = 4, default mode) run twice from the same state: with the
-bias gradients taken from the weight-gradient kernels' K loops (tuning slot 30 = 0, the default) and with the separate
-column sums (slot 30 = 1).  The two differ in the order of fp32 sums only, so every bias-gradient tensor must agree to
-the relative bar tests/test_determinism_gpu.py holds the default mode to against the deterministic one (relative L2
-distance below 1e-3), and the logged scalars to its rtol 1e-4.
+bias gradients taken from the weight-gradient kernels' K loops (tuning slot 30, WGRAD_BIAS_UNFUSED = 0, the default) and
+with the separate column sums (slot 30 = 1).  The two differ in the order of fp32 sums only, so every bias-gradient
+tensor must agree to the relative bar tests/test_determinism_gpu.py holds the default mode to against the deterministic
+one (relative L2 distance below 1e-3), and the logged scalars to its rtol 1e-4.
 
 The call list of the default step (roofline.Attribution) must show the passes gone: no mg_grouped_colsum at all, and
 no mg_colsum_batch descriptor that writes the bias gradient of a fused layer (the discriminator's two convs, the
@@ -13,12 +13,11 @@ import torch
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 E, TOPK, B = 8, 2, 4
-TUNE_WGRAD_BIAS_UNFUSED = 30
 
 
 def _step(unfused):
     import bench
-    from moegan_mi import _lib as L
+    from moegan_mi import ops
     from moegan_mi.init import init_discriminator, init_generator
     from moegan_mi.roofline import Attribution
     from moegan_mi.step import StepConfig, TrainStep
@@ -47,13 +46,10 @@ def _step(unfused):
     fd.normal_(generator=g)
     fg.normal_(generator=g)
     perm = torch.randperm(B, device=DEV, generator=g).int()
-    L.call("mg_set_tuning", TUNE_WGRAD_BIAS_UNFUSED, 1 if unfused else 0)
-    try:
+    with ops.tuning(WGRAD_BIAS_UNFUSED=1 if unfused else 0):
         with Calls() as at:
             out = ts.step(real, text, z, eps_d, eps_g, perm, anneal=3.0, lr_g=2e-4, lr_d=2e-4, eff_kl_weight=1e-8)
         torch.cuda.synchronize()
-    finally:
-        L.call("mg_set_tuning", TUNE_WGRAD_BIAS_UNFUSED, 0)
     assert int(out["flags"][0]) == 0
     scal = {n: out[n].detach().float().cpu().clone() for n in ("d_losses", "r1", "g_gan", "balance", "kl",
                                                                   "g_grad_sumsq", "d_grad_sumsq")}

@@ -79,8 +79,7 @@ for T, C in ((65536, 128), (16384, 256), (4096, 512)):
         t = timed(fn)
         line = f"  {name:30s} {t:7.1f} us  {fl / t / 1e6:6.0f} TF/s"
         if name.startswith("grouped"):  # the same launch on 64^2 tiles (two sub-tiles per dispatch tile)
-            L.call("mg_set_tuning", 3, 64)
-            t64 = timed(fn)
-            L.call("mg_set_tuning", 3, 0)
+            with ops.tuning(GEMM_TILE=64):
+                t64 = timed(fn)
             line += f" | 64x64 {t64:7.1f} us  {fl / t64 / 1e6:6.0f} TF/s"
         print(line, flush=True)

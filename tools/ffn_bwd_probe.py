@@ -43,9 +43,8 @@ def fused():
 
 gf = 2 * 2.0 * n * C * Hd / 1e9
 def fused_2blk():
-    L.call("mg_set_tuning", 14, 2)
-    fused()
-    L.call("mg_set_tuning", 14, 0)
+    with ops.tuning(FFN_BWD_OCC=2):
+        fused()
 
 
 for name, fn in (("unfused gP+gX+colsum", unfused), ("fused (1 block/CU)", fused), ("fused, 2 blocks/CU", fused_2blk)):

@@ -12,13 +12,19 @@ import base64
 import ctypes
 import itertools
 import json
+import os
+import re
 import sys
 import zlib
 
 F32, BF16 = 0, 1  # include/moegan_hip.h MG_F32 / MG_BF16
-# (slot, value) lists; slot numbers: csrc/mg_plan.h
-SETTINGS = [[], [(5, 1)], [(3, 64)], [(3, 128)], [(3, 257)], [(2, 64)], [(2, 128)], [(2, 256)], [(2, 257)], [(9, 2)],
-            [(11, 1)], [(29, 1)], [(16, 1)], [(16, 2)], [(16, 3)]]
+# slot name -> number: the MG_TUNE_* table of include/moegan_hip.h (read as moegan_mi/_lib.py reads it)
+HEADER = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "moegan_hip.h")
+TUNE = {n: int(v) for n, v in re.findall(r"\bMG_TUNE_(\w+)\s*=\s*(\d+)\s*,", open(HEADER).read())}
+# (slot, value) lists
+SETTINGS = [[], [("NO_SLABS", 1)], [("GEMM_TILE", 64)], [("GEMM_TILE", 128)], [("GEMM_TILE", 257)], [("CONV_TILE", 64)],
+            [("CONV_TILE", 128)], [("CONV_TILE", 256)], [("CONV_TILE", 257)], [("SHORTK", 2)], [("DETERMINISTIC", 1)],
+            [("MODGRAD_UNFUSED", 1)], [("NARROW", 1)], [("NARROW", 2)], [("NARROW", 3)]]
 DTYPES = [BF16, F32]
 KS = [1, 3]
 BS = [1, 3, 16, 256]
@@ -32,6 +38,7 @@ def load(path):
     lib = ctypes.CDLL(path)
     i, i64, p = ctypes.c_int, ctypes.c_int64, ctypes.c_void_p
     lib.mg_set_tuning.argtypes = [i, i]
+    lib.mg_get_tuning.argtypes = [i]
     lib.mg_modconv_dgrad_fusable.argtypes = [i] * 8 + [p, i64, p, i64, p, i64]
     lib.mg_conv2d_wgrad_bias_fusable.argtypes = [i, i, i, i, p, i, i, i, i, i]
     lib.mg_gemm_wgrad_bias_fusable.argtypes = [i]
@@ -57,18 +64,19 @@ def pack(bits):
 
 
 def table(lib):
-    """{setting: packed answers}, every slot restored to 0 afterwards."""
+    """{setting (the numeric slot=value spec): packed answers}, every slot restored to what it held."""
     tab = {}
     for setting in SETTINGS:
-        for slot, value in setting:
-            lib.mg_set_tuning(slot, value)
+        held = [(TUNE[name], lib.mg_get_tuning(TUNE[name])) for name, _ in setting]
+        for name, value in setting:
+            lib.mg_set_tuning(TUNE[name], value)
         try:
             bits = answers(lib)
         finally:
-            for slot, _ in setting:
-                lib.mg_set_tuning(slot, 0)
-        tab[",".join(f"{s}={v}" for s, v in setting) or "default"] = {"n": len(bits), "ones": sum(bits),
-                                                                       "bits": pack(bits)}
+            for slot, old in reversed(held):
+                lib.mg_set_tuning(slot, old)
+        tab[",".join(f"{TUNE[n]}={v}" for n, v in setting) or "default"] = {"n": len(bits), "ones": sum(bits),
+                                                                           "bits": pack(bits)}
     return tab
 
 

@@ -188,19 +188,17 @@ def main():
             variants.append((v, kv))
     todo = [(n + (f"[{vn}]" if vn else ""), f, fn, kv) for n, f, fn in cases for vn, kv in variants
             if not only or n in only]
+    slot_name = {num: n for n, num in L.TUNE.items()}  # --variants is the numeric slot=value spec
     for name, flop, fn, kv in todo:
-        for k in range(16):
-            L.call("mg_set_tuning", k, 0)
-        for k, v in kv.items():
-            L.call("mg_set_tuning", k, v)
-        for _ in range(3):
-            fn()
-        ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.iters)]
-        for s, e in ev:
-            s.record()
-            fn()
-            e.record()
-        torch.cuda.synchronize()
+        with ops.tuning(**{slot_name[k]: v for k, v in kv.items()}):
+            for _ in range(3):
+                fn()
+            ev = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in range(a.iters)]
+            for s, e in ev:
+                s.record()
+                fn()
+                e.record()
+            torch.cuda.synchronize()
         ms = sorted(s.elapsed_time(e) for s, e in ev)
         med = ms[len(ms) // 2]
         print(f"{name:20s} {med * 1e3:9.1f} us  {flop / med / 1e9:8.1f} TFLOP/s", flush=True)

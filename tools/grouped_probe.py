@@ -1,5 +1,5 @@
 """Isolated timing of the step's grouped expert GEMMs (8x8 block: 32768 routed rows, C=256, Hd=1024; 4x4 block:
-8192 rows, C=512, Hd=2048; E=8) and the dense short-K projections under the XCD tile-order setting (tuning slot 6:
+8192 rows, C=512, Hd=2048; E=8) and the dense short-K projections under the XCD tile-order setting (tuning slot 6, XCD:
 0 none, 1 every launch), HIP events over 20 launches."""
 import os
 import sys
@@ -50,12 +50,10 @@ for T, C in ((16384, 256), (4096, 512)):
     for name, fn in cases.items():
         res = []
         for v in (0, 1):
-            L.call("mg_set_tuning", 6, v)
+            with ops.tuning(XCD=v):
+                res.append(timed(fn))
+        with ops.tuning(GEMM_TILE=257):  # 128 x 256 tiles
             res.append(timed(fn))
-        L.call("mg_set_tuning", 6, 0)
-        L.call("mg_set_tuning", 3, 257)  # 128 x 256 tiles
-        res.append(timed(fn))
-        L.call("mg_set_tuning", 3, 0)
         print(f"{name:34s} no-xcd {res[0]:6.1f} us  xcd {res[1]:6.1f} us  128x256 {res[2]:6.1f} us", flush=True)
 for M, N, K in ((65536, 384, 128), (65536, 256, 128), (16384, 768, 256), (16384, 512, 256)):
     g = torch.Generator(device=DEV).manual_seed(0)
@@ -64,7 +62,6 @@ for M, N, K in ((65536, 384, 128), (65536, 256, 128), (16384, 768, 256), (16384,
     Cc = torch.empty(M, N, device=DEV, dtype=bf)
     res = []
     for v in (0, 1):
-        L.call("mg_set_tuning", 6, v)
-        res.append(timed(lambda: ops.gemm(A, Bw, M, N, K, out=Cc)))
-    L.call("mg_set_tuning", 6, 0)
+        with ops.tuning(XCD=v):
+            res.append(timed(lambda: ops.gemm(A, Bw, M, N, K, out=Cc)))
     print(f"dense ({M},{N},{K}){'':14s} no-xcd {res[0]:6.1f} us  xcd {res[1]:6.1f} us", flush=True)

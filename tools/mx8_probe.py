@@ -11,7 +11,6 @@ import torch
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(REPO, "moe-gan_cpsc541_amd"))
-from moegan_mi import _lib as L  # noqa: E402
 from moegan_mi import ops  # noqa: E402
 
 SHAPES = [(256, 4, 512, 512), (256, 8, 512, 256), (256, 8, 256, 256), (256, 16, 256, 128), (256, 16, 128, 128)]
@@ -43,10 +42,9 @@ def main():
         t16 = timeit(lambda: ops.conv2d(x, wp, Cout, 3, 3, 1, 1, out=y))
         line = f"B={B} {H}x{H} {Cin}->{Cout}: bf16 {t16:7.1f} us ({fl / t16 / 1e6:6.0f} TF/s)"
         for t in tiles:
-            L.call("mg_set_tuning", 2, t)
-            t8 = timeit(lambda: ops.conv2d_mx8(xq, xsc, wq, wsc, Cout, 3, 3, 1, 1, out=y))
+            with ops.tuning(CONV_TILE=t):
+                t8 = timeit(lambda: ops.conv2d_mx8(xq, xsc, wq, wsc, Cout, 3, 3, 1, 1, out=y))
             line += f" | mx8[{t}] {t8:7.1f} us ({fl / t8 / 1e6:6.0f} TF/s)"
-        L.call("mg_set_tuning", 2, 0)
         tq = timeit(lambda: ops.quant_mx8(x.view(-1, Cin)))
         print(line + f" | quant {tq:6.1f} us ({B * H * H * Cin * 3.03 / tq / 1e3:5.0f} GB/s)", flush=True)
 

@@ -24,10 +24,9 @@ for B, S, C in ((8, 16, 256), (8, 16, 128), (8, 8, 256), (8, 4, 512)):
     ref = ref.permute(0, 2, 3, 1)
     out = {}
     for mode in (0, 1):
-        L.call("mg_set_tuning", 16, mode)
-        for dt in (torch.float32, bf):
-            out[mode, dt] = ops.conv2d(x, wp, 32, 3, 3, 1, 1, out_dtype=dt, ep=ep)
-    L.call("mg_set_tuning", 16, 0)
+        with ops.tuning(NARROW=mode):
+            for dt in (torch.float32, bf):
+                out[mode, dt] = ops.conv2d(x, wp, 32, 3, 3, 1, 1, out_dtype=dt, ep=ep)
     torch.cuda.synchronize()
     for mode, name in ((0, "direct"), (1, "generic")):
         e = (out[mode, torch.float32].double() - ref).abs()

@@ -1,5 +1,5 @@
 """Isolated timing of the MTM offset-head convolutions at the C2 shapes (B=256; 16x16 / 8x8 / 4x4 maps): the direct
-halo-tile kernels (csrc/mg_narrow.hip) against the implicit-GEMM path (tuning slot 16 = 1), HIP events over 20
+halo-tile kernels (csrc/mg_narrow.hip) against the implicit-GEMM path (tuning slot 16, NARROW = 1), HIP events over 20
 launches, with the algorithmic HBM bytes of each call (activation read once, 32-channel side, output)."""
 import os
 import sys
@@ -47,19 +47,16 @@ for S, C in SHAPES:
         "wgrad": (lambda: ops.conv2d_wgrad(ga, x, 32, 3, 3, 1, 1, gw), P * (C + 32) * 2),
     }
     for name, (fn, nbytes) in cases.items():
-        L.call("mg_set_tuning", 16, 1)
-        t_old = timed(fn)
-        L.call("mg_set_tuning", 16, 0)
+        with ops.tuning(NARROW=1):
+            t_old = timed(fn)
         t_new = timed(fn)
         alt = []
-        for blocks in BLOCKS:  # grid-target sweep (tuning slot 17)
-            L.call("mg_set_tuning", 17, blocks)
-            alt.append(timed(fn))
-        L.call("mg_set_tuning", 17, 0)
+        for blocks in BLOCKS:  # grid-target sweep (tuning slot 17, NARROW_BLOCKS)
+            with ops.tuning(NARROW_BLOCKS=blocks):
+                alt.append(timed(fn))
         sweep = "  ".join(f"{b}:{t:5.1f}" for b, t in zip(BLOCKS, alt))
-        if name == "fwd":  # 256-pixel tiles (tuning slot 19 = 4)
-            L.call("mg_set_tuning", 19, 4)
-            sweep += f"  256px: {timed(fn):5.1f}"
-            L.call("mg_set_tuning", 19, 0)
+        if name == "fwd":  # 256-pixel tiles (tuning slot 19, NARROW_WPX = 4)
+            with ops.tuning(NARROW_WPX=4):
+                sweep += f"  256px: {timed(fn):5.1f}"
         print(f"{S:2d}x{S:<2d} C={C:3d} {name:5s} generic {t_old:6.1f} us  direct {t_new:6.1f} us  "
               f"({nbytes / 1e6:5.1f} MB: {nbytes / t_new / 1e6:.2f} TB/s)  {sweep}", flush=True)

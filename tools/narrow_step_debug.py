@@ -8,7 +8,6 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [REPO, os.path.join(REPO, "moe-gan_cpsc541_amd"), os.path.join(REPO, "tests")]
 import torch  # noqa: E402
 
-from moegan_mi import _lib as L  # noqa: E402
 from moegan_mi import ops  # noqa: E402
 from steputil import gpu_step, make_inputs  # noqa: E402
 
@@ -19,9 +18,8 @@ def conv2d(x, wpack, Cout, KH, KW, stride=1, pad=0, **kw):
     if Cout == 32 and KH == 3 and kw.get("out") is None and kw.get("in_scale") is None:
         torch.cuda.synchronize()
         y0 = orig(x, wpack, Cout, KH, KW, stride, pad, **kw)
-        L.call("mg_set_tuning", 16, 1)
-        y1 = orig(x, wpack, Cout, KH, KW, stride, pad, **kw)
-        L.call("mg_set_tuning", 16, 0)
+        with ops.tuning(NARROW=1):
+            y1 = orig(x, wpack, Cout, KH, KW, stride, pad, **kw)
         torch.cuda.synchronize()
         d = (y0.float() - y1.float()).abs()
         print(f"conv Cout=32 x{tuple(x.shape)} stride{x.stride()} contig {x.is_contiguous()} "

@@ -1,6 +1,6 @@
-"""A/B of the router kernel forms (tuning slot 24: 0 MFMA / team forms, 7 lane-FMA forms) on one MX-fp8 C5 test step
-(E = 32 top-4, B = 4, the inputs of tests/test_step_fp8_gpu.py): routing, probabilities and per-tensor gradient
-differences between the two forms.  Diagnostic only."""
+"""A/B of the router kernel forms (tuning slot 24, ROUTER_TEAM: 0 MFMA / team forms, 7 lane-FMA forms) on one MX-fp8 C5
+test step (E = 32 top-4, B = 4, the inputs of tests/test_step_fp8_gpu.py): routing, probabilities and per-tensor
+gradient differences between the two forms.  Diagnostic only."""
 import os
 import sys
 
@@ -9,7 +9,7 @@ for p in (os.path.join(ROOT, "tests"), ROOT, os.path.join(ROOT, "moe-gan_cpsc541
     sys.path.insert(0, p)
 import torch  # noqa: E402
 from steputil import gpu_step, make_inputs  # noqa: E402
-from moegan_mi import _lib as L  # noqa: E402
+from moegan_mi import ops  # noqa: E402
 
 E, topk, B = 32, 4, 4
 real, text, z, eps_d, eps_g, perm = make_inputs(B, E, seed=300 + E)
@@ -17,12 +17,12 @@ cu = lambda t: t.to("cuda")  # noqa: E731
 
 
 def run(slot):
-    L.call("mg_set_tuning", 24, slot)
-    ts = gpu_step(E, topk, "bf16", "cuda", fp8=True)
-    out = ts.step(cu(real), cu(text), cu(z), [tuple(map(cu, e)) for e in eps_d], [tuple(map(cu, e)) for e in eps_g],
-                  cu(perm.int()), anneal=3.0, lr_g=2e-4, lr_d=2e-4, eff_kl_weight=0.001 * 1e-5)
-    torch.cuda.synchronize()
-    L.call("mg_set_tuning", 24, 0)
+    with ops.tuning(ROUTER_TEAM=slot):
+        ts = gpu_step(E, topk, "bf16", "cuda", fp8=True)
+        out = ts.step(cu(real), cu(text), cu(z), [tuple(map(cu, e)) for e in eps_d],
+                      [tuple(map(cu, e)) for e in eps_g], cu(perm.int()), anneal=3.0, lr_g=2e-4, lr_d=2e-4,
+                      eff_kl_weight=0.001 * 1e-5)
+        torch.cuda.synchronize()
     return ts, {k: ([t.detach().cpu().clone() for t in v] if isinstance(v, (list, tuple)) else
                     v.detach().cpu().clone() if torch.is_tensor(v) else v) for k, v in out.items()}
 

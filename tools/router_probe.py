@@ -1,6 +1,7 @@
 """Isolated timings of the router kernels at the C5 layer shapes (32 experts top-4; 4x4 / 8x8 / 16x16 tokens of
-batch 256): router forward (MFMA vs team kernel, tuning slot 24), router backward (teams vs thread per token) and
-the token gradient.  Diagnostic only; times are HIP-event averages over 50 launches (launch overhead included)."""
+batch 256): router forward (MFMA vs team kernel, tuning slot 24, ROUTER_TEAM), router backward (teams vs thread per
+token) and the token gradient.  Diagnostic only; times are HIP-event averages over 50 launches (launch overhead
+included)."""
 import os
 import sys
 
@@ -8,7 +9,6 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "moe-gan_cpsc541_amd"))
 import torch  # noqa: E402
 from moegan_mi import ops  # noqa: E402
-from moegan_mi import _lib as L  # noqa: E402
 
 DEV = "cuda"
 E, k, B = 32, 4, 256
@@ -35,17 +35,15 @@ for HW, C in ((16, 512), (64, 256), (256, 128)):
     temp = torch.tensor([1.0], device=DEV)
     row = {}
     for slot in (0, 1):
-        L.call("mg_set_tuning", 24, slot)
-        row[f"fwd{'_team' if slot else '_mfma'}"] = timed(lambda: ops.router_fwd(tok, Wfc, Lt, E, k, HW, temp, 1.0))
-    L.call("mg_set_tuning", 24, 0)
+        with ops.tuning(ROUTER_TEAM=slot):
+            row[f"fwd{'_team' if slot else '_mfma'}"] = timed(lambda: ops.router_fwd(tok, Wfc, Lt, E, k, HW, temp, 1.0))
     probs, zlog, topi, gate = ops.router_fwd(tok, Wfc, Lt, E, k, HW, temp, 1.0)
     g_gate = torch.randn(T, k, device=DEV, generator=g)
     gt = torch.zeros(1, device=DEV)
     for slot in (0, 2):
-        L.call("mg_set_tuning", 24, slot)
-        row[f"bwd{'_thread' if slot else '_team'}"] = timed(
-            lambda: ops.router_bwd(probs, zlog, topi, gate, g_gate, None, None, HW, temp, 1.0, gt, B))
-    L.call("mg_set_tuning", 24, 0)
+        with ops.tuning(ROUTER_TEAM=slot):
+            row[f"bwd{'_thread' if slot else '_team'}"] = timed(
+                lambda: ops.router_bwd(probs, zlog, topi, gate, g_gate, None, None, HW, temp, 1.0, gt, B))
     g_raw = torch.randn(T, E, device=DEV, generator=g)
     gX = torch.randn(T * k, C, device=DEV, generator=g).to(torch.bfloat16)
     pos_of = torch.randperm(T * k, device=DEV, generator=g).to(torch.int32)

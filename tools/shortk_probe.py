@@ -1,6 +1,7 @@
 """Isolated timing of the step's short-K GEMMs (K = 128 .. 384 over 16K-64K token rows: the attention / MoE
-projections and the 1x1 skip convs) under each tile override (tuning slot 3: 0 automatic, 64, 128, 256 = 256x128,
-257 = 128x256), HIP events over 20 launches, with the algorithmic HBM bytes (A + B read once, C written once)."""
+projections and the 1x1 skip convs) under each tile override (tuning slot 3, GEMM_TILE: 0 automatic, 64, 128, 256 =
+256x128, 257 = 128x256), HIP events over 20 launches, with the algorithmic HBM bytes (A + B read once, C written
+once)."""
 import os
 import sys
 
@@ -8,7 +9,6 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [REPO, os.path.join(REPO, "moe-gan_cpsc541_amd")]
 import torch  # noqa: E402
 
-from moegan_mi import _lib as L  # noqa: E402
 from moegan_mi import ops  # noqa: E402
 
 DEV, bf = "cuda", torch.bfloat16
@@ -40,9 +40,8 @@ for M, N, K, akc, bkc, has_bias in SHAPES:
     mb = (M * K + N * K + M * N) * 2 / 1e6
     res = []
     for tile in (0, 64, 128, 256, 257):
-        L.call("mg_set_tuning", 3, tile)
-        res.append(timed(lambda: ops.gemm(A, B, M, N, K, a_kc=bool(akc), b_kc=bool(bkc), out=C, ep=ep)))
-    L.call("mg_set_tuning", 3, 0)
+        with ops.tuning(GEMM_TILE=tile):
+            res.append(timed(lambda: ops.gemm(A, B, M, N, K, a_kc=bool(akc), b_kc=bool(bkc), out=C, ep=ep)))
     print(f"({M:5d},{N:4d},{K:4d}) kc={akc}{bkc} " + "  ".join(f"{t}:{r:6.1f}" for t, r in
                                                              zip(("auto", 64, 128, 256, 257), res)) +
           f" us  ({mb:.0f} MB: {mb / min(res):.2f} TB/s best)", flush=True)

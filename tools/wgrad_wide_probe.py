@@ -9,7 +9,6 @@ REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path[:0] = [REPO, os.path.join(REPO, "moe-gan_cpsc541_amd")]
 import torch  # noqa: E402
 
-from moegan_mi import _lib as L  # noqa: E402
 from moegan_mi import ops  # noqa: E402
 
 DEV = "cuda"
@@ -38,24 +37,22 @@ for M, N, K in SHAPES:
     C = torch.zeros(M, N, device=DEV)
     fn = lambda: ops.gemm(A, B, M, N, K, a_kc=False, b_kc=False, out=C, ep=ops.E(atomic=1), splits=0)  # noqa
     res = {}
-    L.call("mg_set_tuning", 15, 1)
-    res["generic"] = timeit(fn)
-    C.zero_()
-    fn()
-    ref = C.clone()
-    errs = []
-    for mode in MODES:
-        L.call("mg_set_tuning", 15, mode)
-        for tb in (128, 256, 512):
-            L.call("mg_set_tuning", 27, tb)
-            res[f"{'w' if mode == 2 else 'w256'}/{tb}"] = timeit(fn)
-        L.call("mg_set_tuning", 27, 0)
+    with ops.tuning(WIDE_WGRAD=1):
+        res["generic"] = timeit(fn)
         C.zero_()
         fn()
-        torch.cuda.synchronize()
+        ref = C.clone()
+    errs = []
+    for mode in MODES:
+        with ops.tuning(WIDE_WGRAD=mode):
+            for tb in (128, 256, 512):
+                with ops.tuning(WIDE_BLOCKS=tb):
+                    res[f"{'w' if mode == 2 else 'w256'}/{tb}"] = timeit(fn)
+            C.zero_()
+            fn()
+            torch.cuda.synchronize()
         errs.append(((C - ref).norm() / ref.norm()).item())
     err = max(errs)
-    L.call("mg_set_tuning", 15, 0)
     res["auto"] = timeit(fn)
     mb = K * (M + N) * 2 / 1e6
     best = min(v for k_, v in res.items() if k_.startswith("w"))
