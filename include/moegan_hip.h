@@ -330,6 +330,46 @@ int mg_clip_contrast(const float* f, int64_t ldf, int B, const float* t, int64_t
                      float tau, const float* scale, double* work, int64_t nwork, float* loss, float* g_f,
                      void* stream);
 
+/* Vision-aided discriminator head on frozen image features (no reference counterpart; Kumari et al., GigaGAN's
+   L_vision, StyleGAN-T).  x: an fp32 feature row, c: an fp32 caption row, both C wide, C = 64 or 512; H a multiple of
+   64 in [64, 512]; W1 [H, C], b1 [H], Wt [H, C], bt [H], w2 [H], b2 [1], all fp32:
+     x~ = sqrt(C) x / |x|     c~ = sqrt(C) c / |c|
+     a  = W1 x~ + b1          h  = a > 0 ? a : 0.2 a          e = Wt c~ + bt
+     logit(x, c) = <w2, h> + b2 + <h, e> / sqrt(H)
+   A row is dead when its squared norm is zero or not finite; a pairing with a dead member (or, where a row index is
+   given, an index outside [0, rows): it is never used as an address) has logit 0, adds 0 to every sum and takes and
+   gives no gradient; divisors stay B.  The raw dots <W1_j, x>, <Wt_j, c>, the weight-gradient products and W1^T g_a
+   run on the exact-fp32 MFMA chain of mg_poly_mmd_sums in 64 x 64 tiles; everything after a dot is fp64 in a fixed
+   order.  No atomics, bitwise repeatable, independent of every tuning slot; launch counts and grids depend on
+   (rows, C, H) alone.  `work` is caller-owned, 16-byte aligned device memory of
+     nwork >= 10 B + 13 B H / 2 + 8 (H + C) ceil(B / 4) + C H / 2   doubles       (B = n for mg_vhead_logits)
+   for every entry; no other memory is used.  Nothing is written when an argument is refused.
+
+   mg_vhead_logits: logits[i] = logit(x_i, t_{idx ? idx[i] : i}) for i < n; hidden (optional, fp32 [n, H]) = h of
+   row i (zeros for a dead feature row). */
+int mg_vhead_logits(const float* x, int64_t ldx, const float* t, int64_t ldt, const int32_t* idx, int n, int C, int H,
+                    const float* W1, const float* b1, const float* Wt, const float* bt, const float* w2,
+                    const float* b2, double* work, int64_t nwork, float* logits, float* hidden, void* stream);
+
+/* Discriminator side: with lr_b = logit(xr_b, t_b), lf_b = logit(xf_b, t_b), lm_b = logit(xr_b, t_perm[b]),
+     out[0] = (1 / B) sum_b [softplus(-lr_b) + softplus(lf_b) + softplus(lm_b)],  out[1..3] = the three means,
+   real_pred / fake_pred / mism_pred [B] = the logits, and the gradients of out[0] with respect to the six
+   parameters are ADDED into dW1 [H, C], db1 [H], dWt [H, C], dbt [H], dw2 [H], db2 [1] (fp32).  No gradient goes
+   to features or captions.  The mismatched pairing reaches dWt by gathering c~[perm[b]] as extra operand rows. */
+int mg_vhead_d(const float* xr, int64_t ldr, const float* xf, int64_t ldf, const float* t, int64_t ldt,
+               const int32_t* perm, int B, int C, int H, const float* W1, const float* b1, const float* Wt,
+               const float* bt, const float* w2, const float* b2, double* work, int64_t nwork, float* out,
+               float* real_pred, float* mism_pred, float* fake_pred, float* dW1, float* db1, float* dWt, float* dbt,
+               float* dw2, float* db2, void* stream);
+
+/* Generator side: loss[0] = (1 / B) sum_b softplus(-logit(xf_b, t_b)), fake_pred [B] = the logits, and
+   g_x [B, C] (fp32, contiguous) = scale[0] d loss / d xf through the normalisation (sqrt(C) / |x|)(I - x^ x^T);
+   scale is a device scalar.  No parameter gradients. */
+int mg_vhead_g(const float* xf, int64_t ldf, const float* t, int64_t ldt, int B, int C, int H, const float* W1,
+               const float* b1, const float* Wt, const float* bt, const float* w2, const float* b2,
+               const float* scale, double* work, int64_t nwork, float* loss, float* fake_pred, float* g_x,
+               void* stream);
+
 /* LayerNorm over C (128/256/512/768) per row (+ optional LeakyReLU), saving mean/rstd. t2i_moe_gan.py:505-507, :684. */
 int mg_layernorm_fwd(int dtype, const void* x, int64_t ldx, int R, int C, const float* gamma, const float* beta, float eps, void* y, int64_t ldy, float* mean, float* rstd, int act, void* stream);
 

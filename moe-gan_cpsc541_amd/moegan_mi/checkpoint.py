@@ -85,7 +85,7 @@ def load_optimizer_state_dict(store, sd):
 
 
 def save_resume(path, generator, discriminator, epoch, step, lr_g, lr_d, betas=(0.5, 0.999), epoch_complete=False,
-                generators=None):
+                generators=None, vision_head=None):
     """Write the reference's resume layout (t2i_moe_gan.py:1484-1491) with only the reference's keys.  ``epoch``
     is the 0-based epoch the state belongs to.  A mid-epoch checkpoint stores it as is (:1489); an end-of-epoch
     one (``epoch_complete``) stores ``epoch + 1``, as the reference's end-of-epoch file does (:1648), so a tool
@@ -93,13 +93,19 @@ def save_resume(path, generator, discriminator, epoch, step, lr_g, lr_d, betas=(
     state (or the generator itself) stored as ``rng/<name>``, so a resumed run continues the same z, permutation
     and router-noise streams (every rank's local stream under data parallelism: ``rng/local<r>``).
     A generator that keeps a moving average (``ParamStore.enable_ema``) adds one key, ``generator_ema``: the
-    averaged weights as a state dict in the reference's names.  Without one the key set is the reference's."""
+    averaged weights as a state dict in the reference's names.  Without one the key set is the reference's.
+    ``vision_head`` (a module with ``state_dict()`` and the head's ``_store``, t2i_moe_gan.VisionAidedDiscriminator):
+    two more keys, ``vision_head`` and ``optimizer_v`` (its AdamW state at ``lr_d``); without a head neither is
+    written."""
     ck = {"generator": generator.state_dict(), "discriminator": discriminator.state_dict(),
           "optimizer_g": optimizer_state_dict(generator._store, lr_g, betas),
           "optimizer_d": optimizer_state_dict(discriminator._store, lr_d, betas),
           "epoch": int(epoch) + (1 if epoch_complete else 0), "step": int(step)}
     if generator._store.ema is not None:  # this build's extension: the averaged generator, in the reference's names
         ck["generator_ema"] = generator._store.ema_state_dict(cpu=False)
+    if vision_head is not None:  # this build's extension: the vision-aided discriminator head and its optimizer
+        ck["vision_head"] = vision_head.state_dict()
+        ck["optimizer_v"] = optimizer_state_dict(vision_head._store, lr_d, betas)
     for name, g in (generators or {}).items():
         ck["rng/" + name] = g.get_state() if hasattr(g, "get_state") else g
     torch.save(ck, path)
@@ -124,12 +130,13 @@ def _load_ema(store, sd):
             store.ema.copy_(store.data)
 
 
-def load_resume(path, generator, discriminator, generators=None):
+def load_resume(path, generator, discriminator, generators=None, vision_head=None):
     """Load a resume checkpoint (ours or the reference's); returns (start epoch, step).  A model-only checkpoint
     ({'generator', 'discriminator'}) or a bare generator state dict loads the weights and returns (0, 0).
     ``generators``: name -> torch.Generator restored from the checkpoint's ``rng/<name>`` states when present.
     A generator that keeps a moving average takes it from ``generator_ema``; from a file without that key the
-    average starts at the loaded weights."""
+    average starts at the loaded weights.  ``vision_head``: restored from ``vision_head`` / ``optimizer_v``; a file
+    without them leaves the head as it is (a fresh one) and says so in the log."""
     ck = torch.load(path, map_location="cpu", weights_only=True)
     if "generator" not in ck:  # bare generator state dict (inference.py:44-49)
         generator.load_state_dict(ck)
@@ -143,6 +150,13 @@ def load_resume(path, generator, discriminator, generators=None):
         load_optimizer_state_dict(generator._store, ck["optimizer_g"])
     if "optimizer_d" in ck:
         load_optimizer_state_dict(discriminator._store, ck["optimizer_d"])
+    if vision_head is not None:
+        if "vision_head" in ck:
+            vision_head.load_state_dict(ck["vision_head"])
+            if "optimizer_v" in ck:
+                load_optimizer_state_dict(vision_head._store, ck["optimizer_v"])
+        else:
+            logger.info("checkpoint has no 'vision_head': the vision-aided head starts fresh")
     for name, g in (generators or {}).items():
         st = ck.get("rng/" + name)
         if st is not None:

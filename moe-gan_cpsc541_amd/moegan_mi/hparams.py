@@ -17,9 +17,9 @@ import json
 INT_KEYS = ("batch_size", "epochs", "kl_annealing_epochs", "lr_warmup_epochs", "eval_every", "eval_samples",
             "eval_nearest_k")
 FLOAT_KEYS = ("learning_rate", "beta1", "beta2", "r1_gamma", "clip_weight_16", "clip_weight_8", "kl_weight",
-              "balance_weight", "ema_kimg", "ema_rampup", "clip_temperature")
+              "balance_weight", "ema_kimg", "ema_rampup", "clip_temperature", "vision_weight")
 # this build's switches: "true" / "1" / "yes" / "on" (any case) turn one on, "false" / "0" / "no" / "off" / "" off
-BOOL_KEYS = ("eval_frechet", "clip_contrastive")
+BOOL_KEYS = ("eval_frechet", "clip_contrastive", "vision_d")
 # this build's policy strings: "" / "none" / "off" / "false" / "0" (any case) mean off (None), anything else is kept
 # (stripped) for the training entry point to validate
 POLICY_KEYS = ("diffaug",)
@@ -57,6 +57,10 @@ TRAIN_KWARGS = {
     # clip_temperature (0.07 = CLIP's initial temperature: a choice, not a measurement); off unless set
     "clip_contrastive": ("clip_contrastive", False),
     "clip_temperature": ("clip_temperature", 0.07),
+    # this build's extension: with clip_grad, a vision-aided discriminator head on the frozen image tower's features,
+    # its generator-side loss weighted by vision_weight (1.0: a choice, not a measurement); off unless set
+    "vision_d": ("vision_d", False),
+    "vision_weight": ("vision_weight", 1.0),
 }
 # fixed by the SageMaker entry point (sagemaker_train.py:287-292)
 TRAIN_FIXED = {"log_interval": 100, "save_interval": 500, "gradient_accumulation_steps": 8,

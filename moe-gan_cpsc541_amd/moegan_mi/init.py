@@ -65,6 +65,21 @@ def init_generator(store, seed=0):
     store.load_state_dict(sd)
 
 
+def init_vision_head(store, seed=2):
+    """The vision-aided head (layout.vision_head_shapes): fc.weight and text_proj.weight ~ U(+-1/sqrt(C)),
+    out.weight ~ U(+-1/sqrt(H)), every bias zero.  Choices of this build (nn.Linear's weight bounds with zero
+    biases, so a fresh head's logit starts near 0), not taken from a paper or a measurement."""
+    gen = torch.Generator(device="cpu").manual_seed(seed)
+    sd = {}
+    for n, shp in store.shapes.items():
+        t = torch.zeros(shp)
+        if n.endswith("weight"):
+            b = 1.0 / math.sqrt(shp[1])
+            t.uniform_(-b, b, generator=gen)
+        sd[n] = t
+    store.load_state_dict(sd)
+
+
 def init_discriminator(store, seed=1):
     gen = torch.Generator(device="cpu").manual_seed(seed)
     sd = {}

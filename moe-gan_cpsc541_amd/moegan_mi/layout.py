@@ -155,5 +155,28 @@ def discriminator_shapes():
     return d
 
 
+VISION_HEAD_KEYS = ("fc.weight", "fc.bias", "text_proj.weight", "text_proj.bias", "out.weight", "out.bias")
+
+
+def vision_head_shapes(C=512, H=256):
+    """Ordered ``{state_dict key: shape}`` of the vision-aided discriminator head (this build's extension, no
+    reference counterpart; include/moegan_hip.h has the definition): a LeakyReLU layer ``fc`` on the normalised
+    image feature, the caption projection ``text_proj`` and the read-out ``out``.  ``C`` is the feature width (64 or
+    512), ``H`` the hidden width (a multiple of 64 in [64, 512]; 256 is a choice)."""
+    C, H = int(C), int(H)
+    if C not in (64, 512):
+        raise ValueError(f"vision head: the feature width must be 64 or 512, got {C}")
+    if H % 64 or not 64 <= H <= 512:
+        raise ValueError(f"vision head: the hidden width must be a multiple of 64 in [64, 512], got {H}")
+    d = OrderedDict()
+    d["fc.weight"] = (H, C)
+    d["fc.bias"] = (H,)
+    d["text_proj.weight"] = (H, C)
+    d["text_proj.bias"] = (H,)
+    d["out.weight"] = (1, H)
+    d["out.bias"] = (1,)
+    return d
+
+
 def is_buffer(name):
     return name.rsplit(".", 1)[-1] in BUFFER_SUFFIXES

@@ -1314,6 +1314,121 @@ def clip_contrast(f, t, tau, scale, pos_off=0, loss=None, g_f=None):
     return loss, g_f
 
 
+VHEAD_KEYS = ("fc.weight", "fc.bias", "text_proj.weight", "text_proj.bias", "out.weight", "out.bias")
+
+
+def vhead_work(B, C, H):
+    """Doubles the three mg_vhead_* entries need in their workspace (include/moegan_hip.h)."""
+    return 10 * B + 13 * B * H // 2 + 8 * (H + C) * (-(-B // 4)) + C * H // 2
+
+
+def _vhead_params(params, what):
+    """The six head tensors in VHEAD_KEYS order from a mapping (or a sequence in that order), checked: fp32 device
+    tensors, contiguous, fc / text_proj [H, C] 16-byte aligned, the vectors H long.  Returns (tensors, C, H)."""
+    ts = [params[k] for k in VHEAD_KEYS] if hasattr(params, "keys") else list(params)
+    if len(ts) != 6:
+        raise L.MGError(f"{what}: expected the six head tensors {VHEAD_KEYS}")
+    W1 = ts[0]
+    if W1.dim() != 2:
+        raise L.MGError(f"{what}: fc.weight must be [H, C], got {tuple(W1.shape)}")
+    H, C = W1.shape
+    want = ((H, C), (H,), (H, C), (H,), (1, H), (1,))
+    for k, t, shp in zip(VHEAD_KEYS, ts, want):
+        if t.dtype != torch.float32 or not t.is_cuda or tuple(t.shape) != shp or not t.is_contiguous():
+            raise L.MGError(f"{what}: {k} must be a contiguous fp32 device tensor {shp}, got {tuple(t.shape)} "
+                            f"{t.dtype} {t.device}")
+    if W1.data_ptr() % 16 or ts[2].data_ptr() % 16:
+        raise L.MGError(f"{what}: fc.weight / text_proj.weight must be 16-byte aligned")
+    return ts, C, H
+
+
+def _vhead_rows(x, C, B, what, name):
+    x = _feature_rows(x, f"{what}: {name}")
+    if tuple(x.shape) != (B, C):
+        raise L.MGError(f"{what}: {name} must be [{B}, {C}], got {tuple(x.shape)}")
+    return x
+
+
+def _vhead_workspace(B, C, H, device):
+    need = vhead_work(max(B, 1), C, H)
+    return (zeros(need, device=device, dtype=torch.float64) if ARENA.active
+            else torch.empty(need, device=device, dtype=torch.float64))
+
+
+def _vhead_out(t, shape, device, what, name):
+    if t is None:
+        return torch.empty(shape, device=device)
+    if t.dtype != torch.float32 or tuple(t.shape) != tuple(shape) or not t.is_contiguous() or not t.is_cuda:
+        raise L.MGError(f"{what}: {name} must be contiguous fp32 {tuple(shape)} on the device")
+    return t
+
+
+def vhead_logits(x, t, params, idx=None, want_hidden=False):
+    """Logits of the vision-aided head (include/moegan_hip.h) for image features x [n, C] against caption features
+    t [n, C] (row idx[i] of t when the int32 ``idx`` [n] is given; an index outside [0, n) is a dead pairing):
+    mg_vhead_logits, forward only.  ``params``: the six head tensors by name.  Returns logits [n], or
+    (logits, hidden [n, H]) with ``want_hidden``."""
+    ps, C, H = _vhead_params(params, "vhead_logits")
+    n = x.shape[0] if x.dim() == 2 else -1
+    x, t = _vhead_rows(x, C, n, "vhead_logits", "x"), _vhead_rows(t, C, n, "vhead_logits", "t")
+    if idx is not None and (idx.dtype != torch.int32 or tuple(idx.shape) != (n,) or not idx.is_contiguous()
+                            or not idx.is_cuda):
+        raise L.MGError(f"vhead_logits: idx must be a contiguous int32 device tensor [{n}]")
+    logits = torch.empty(n, device=x.device)
+    hidden = torch.empty(n, H, device=x.device) if want_hidden else None
+    work = _vhead_workspace(n, C, H, x.device)
+    call("mg_vhead_logits", ptr(x), x.stride(0), ptr(t), t.stride(0), ptr(idx), n, C, H, *[ptr(p) for p in ps],
+         ptr(work), work.numel(), ptr(logits), ptr(hidden), S())
+    return (logits, hidden) if want_hidden else logits
+
+
+def vhead_d(xr, xf, t, perm, params, grads, out=None, real_pred=None, mism_pred=None, fake_pred=None):
+    """Discriminator-side loss of the vision-aided head over real features xr, fake features xf and captions t (all
+    fp32 [B, C]; perm int32 [B] names each real row's mismatched caption): out [4] = (L_d, real, fake, mismatched
+    term), the three logit vectors, and the six parameter gradients ADDED into ``grads`` (tensors by the names of
+    ``params``) -- mg_vhead_d.  No gradient reaches features or captions.  Returns (out, real_pred, mism_pred,
+    fake_pred)."""
+    ps, C, H = _vhead_params(params, "vhead_d")
+    gs, Cg, Hg = _vhead_params(grads, "vhead_d (grads)")
+    if (Cg, Hg) != (C, H):
+        raise L.MGError(f"vhead_d: the gradients are for (C, H) = ({Cg}, {Hg}), the head is ({C}, {H})")
+    B = xr.shape[0] if xr.dim() == 2 else -1
+    xr, xf, t = (_vhead_rows(v, C, B, "vhead_d", n) for v, n in ((xr, "xr"), (xf, "xf"), (t, "t")))
+    if perm.dtype != torch.int32 or tuple(perm.shape) != (B,) or not perm.is_contiguous() or not perm.is_cuda:
+        raise L.MGError(f"vhead_d: perm must be a contiguous int32 device tensor [{B}]")
+    dev = xr.device
+    out = _vhead_out(out, (4,), dev, "vhead_d", "out")
+    real_pred = _vhead_out(real_pred, (B,), dev, "vhead_d", "real_pred")
+    mism_pred = _vhead_out(mism_pred, (B,), dev, "vhead_d", "mism_pred")
+    fake_pred = _vhead_out(fake_pred, (B,), dev, "vhead_d", "fake_pred")
+    work = _vhead_workspace(B, C, H, dev)
+    call("mg_vhead_d", ptr(xr), xr.stride(0), ptr(xf), xf.stride(0), ptr(t), t.stride(0), ptr(perm), B, C, H,
+         *[ptr(p) for p in ps], ptr(work), work.numel(), ptr(out), ptr(real_pred), ptr(mism_pred), ptr(fake_pred),
+         *[ptr(g) for g in gs], S())
+    return out, real_pred, mism_pred, fake_pred
+
+
+def vhead_g(xf, t, params, scale, loss=None, fake_pred=None, g_x=None):
+    """Generator-side loss of the vision-aided head, (1 / B) sum_b softplus(-logit(xf_b, t_b)), its logits and
+    g_x = scale * d loss / d xf through the feature normalisation (mg_vhead_g); ``scale`` is one fp32 device scalar.
+    No parameter gradients: the reference's accumulation "leak" of its G loss into the discriminator's gradients is
+    deliberately not reproduced for the head, there is no R1 on it (Kumari et al. use none), and it sees un-augmented
+    images (DiffAugment in front of the tower is out of scope).  Returns (loss [1], fake_pred [B], g_x [B, C])."""
+    ps, C, H = _vhead_params(params, "vhead_g")
+    B = xf.shape[0] if xf.dim() == 2 else -1
+    xf, t = _vhead_rows(xf, C, B, "vhead_g", "xf"), _vhead_rows(t, C, B, "vhead_g", "t")
+    if not torch.is_tensor(scale) or scale.dtype != torch.float32 or scale.numel() != 1 or not scale.is_cuda:
+        raise L.MGError("vhead_g: scale must be one fp32 device scalar")
+    dev = xf.device
+    loss = _vhead_out(loss, (1,), dev, "vhead_g", "loss")
+    fake_pred = _vhead_out(fake_pred, (B,), dev, "vhead_g", "fake_pred")
+    g_x = _vhead_out(g_x, (B, C), dev, "vhead_g", "g_x")
+    work = _vhead_workspace(B, C, H, dev)
+    call("mg_vhead_g", ptr(xf), xf.stride(0), ptr(t), t.stride(0), B, C, H, *[ptr(p) for p in ps], ptr(scale),
+         ptr(work), work.numel(), ptr(loss), ptr(fake_pred), ptr(g_x), S())
+    return loss, fake_pred, g_x
+
+
 def g_loss(fake, out, g, scale=1.0):
     call("mg_g_loss", ptr(fake), fake.shape[0], scale, ptr(out), ptr(g), S())
 

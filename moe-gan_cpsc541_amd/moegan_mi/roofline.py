@@ -64,6 +64,9 @@ FAMILIES = {
     # contrastive CLIP loss (mg_contrast.hip): B x N logits recomputed tile by tile, never stored; at the step's batch
     # sizes its five launches are latency-sized, so it is priced by the bytes it has to move
     "clip_contrast": ("hbm", ("mg_clip_contrast",)),
+    # vision-aided discriminator head (mg_vhead.hip): small fp32 MFMA products around fp64 row kernels; at the step's
+    # batch sizes its launches are latency-sized, so it is priced by the bytes it has to move
+    "vision_head": ("hbm", ("mg_vhead_logits", "mg_vhead_d", "mg_vhead_g")),
 }
 _FAMILY_OF = {e: f for f, (_, es) in FAMILIES.items() for e in es}
 
@@ -104,6 +107,7 @@ KERNELS = [
      r"k_cos_loss",
      "losses_flags"),
     (r"k_contrast_norms|k_contrast_stats|k_contrast_fold|k_contrast_grad|k_contrast_apply", "clip_contrast"),
+    (r"k_vh_", "vision_head"),
 ]
 
 
@@ -342,6 +346,18 @@ def work(name, a):
         S = max(1, min(tiles, 8, -(-512 // strips)))
         rows = (B + N) + 2 * B * S + 3 * strips * N
         return 4.0 * C * (rows + B) + (16.0 * B * C * S if S > 1 else 8.0 * B * C) + 8.0 * (4 * B + N + 4 * B * S)
+    if name in ("mg_vhead_logits", "mg_vhead_d", "mg_vhead_g"):
+        # feature sets and the two weight matrices read once, the raw dots written and read once; the D entry adds
+        # its fp64 row gradients (written, read by the fold), the transposed operands (written, read) and the two
+        # weight gradients (read, written); the G entry the transposed W1, u and the feature gradient
+        B, C, H = a["n" if name == "mg_vhead_logits" else "B"], a["C"], a["H"]
+        sets = {"mg_vhead_logits": 2, "mg_vhead_d": 3, "mg_vhead_g": 2}[name]
+        b = 4.0 * (sets * B * C + 2 * H * C) + 8.0 * sets * B * H
+        if name == "mg_vhead_d":
+            b += 16.0 * 5 * B * H + 8.0 * (H + C) * 2 * B + 16.0 * H * C
+        if name == "mg_vhead_g":
+            b += 8.0 * B * H + 8.0 * H * C + 12.0 * B * C
+        return b
     if name == "mg_finite_flag":
         return 4.0 * a["n"]
     if name == "mg_kl_coefs":

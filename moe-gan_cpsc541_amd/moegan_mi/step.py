@@ -23,6 +23,19 @@ to_rgb then trains, so the store keeps it inside the optimised range (layout.fro
 captions with the image's own caption as the positive (mg_clip_contrast; under data parallelism the captions are
 gathered once per step, the features are not); the tower passes, the weights, the guard and the logged keys stay.
 
+``StepConfig(clip_grad=True, vision_d=True)`` (this build's extension, off by default) adds a vision-aided
+discriminator head (Kumari et al., "Ensembling off-the-shelf models for GAN training"; GigaGAN's L_vision; StyleGAN-T's
+frozen-feature discriminator): a small conditional head (include/moegan_hip.h, ``mg_vhead_*``) that judges images in the
+feature space of the frozen image tower.  It has its own parameter store ``TrainStep.vs`` (layout.vision_head_shapes)
+and its own gated AdamW launch with ``lr_d`` / ``d_clip`` and its own step counter.  D phase: one forward-only tower
+pass over the real batch and the D-phase fakes together, then ops.vhead_d (real / fake / mismatched-caption softplus
+terms, the three of mg_d_loss) into ``vs.grad``; a non-finite head loss skips the batch like a non-finite d_loss.
+G phase: ops.vhead_g on the tower features of img16 that the CLIP term already computed, with the head as this step's
+D phase updated it; its feature gradient times ``vision_weight`` joins the CLIP term's before the one tower backward
+that already runs (img8 gets no vision term).  The head sees un-augmented images (DiffAugment in front of the tower
+is out of scope), has no R1 (Kumari et al. use none), and the reference's accumulation "leak" of the G loss into D's
+gradients is deliberately not reproduced for it: ``vs.grad`` only ever holds d L_d.
+
 Loss guards (t2i_moe_gan.py:1315-1320, :1367-1376, :1396-1404) run on the device: a flag word per step
 (``out["flags"]``) records a non-finite discriminator loss (the whole batch is skipped: no gradient is
 kept, no optimizer steps, no step counters advance) or a non-finite generator loss (replaced by 0: only
@@ -46,7 +59,7 @@ import torch.nn.functional as F
 from . import graphs, ops
 from .engine_d import DiscriminatorEngine
 from .engine_g import GeneratorEngine
-from .layout import discriminator_shapes, frozen_rgb_prefixes, generator_shapes
+from .layout import discriminator_shapes, frozen_rgb_prefixes, generator_shapes, vision_head_shapes
 from .params import ParamStore
 
 FD, FG = ops.FLAG_D_BAD, ops.FLAG_G_BAD
@@ -56,8 +69,14 @@ class StepConfig:
     def __init__(self, E=4, topk=None, dtype="fp32", r1_gamma=10.0, clip_weight_16=0.1, clip_weight_8=0.05,
                  balance_weight=0.01, beta1=0.5, beta2=0.999, weight_decay=0.01, eps=1e-8, d_clip=0.7, g_clip=0.8,
                  psi=0.7, fp8=False, max_res=16, deterministic=None, clip_grad=False, ema_halflife=None,
-                 ema_rampup=None, diffaug=None, clip_loss="cosine", clip_temperature=0.07):
-        """``clip_loss`` (with ``clip_grad=True``): "cosine" = the reference's 1 - mean cos(image, own caption);
+                 ema_rampup=None, diffaug=None, clip_loss="cosine", clip_temperature=0.07, vision_d=False,
+                 vision_weight=1.0, vision_hidden=256):
+        """``vision_d`` (needs ``clip_grad=True``: the head's generator gradient goes through the build's own tower
+        backward): the vision-aided discriminator head of the module docstring, hidden width ``vision_hidden`` (a
+        multiple of 64 in [64, 512]; 256 is a choice); its generator-side loss enters with ``vision_weight`` (finite,
+        >= 0).  The default 1.0 -- the adversarial term's own weight -- is a choice, not a measurement.
+
+        ``clip_loss`` (with ``clip_grad=True``): "cosine" = the reference's 1 - mean cos(image, own caption);
         "contrastive" = a softmax over the (global) batch's captions with the image's own caption as the positive
         (ops.clip_contrast), at temperature ``clip_temperature``.  The default 0.07 is CLIP's initial temperature: a
         choice, not a measurement -- it is explicit because the weight loaders drop the checkpoint's logit_scale."""
@@ -87,6 +106,16 @@ class StepConfig:
         if not float(clip_temperature) > 0 or float(clip_temperature) == float("inf"):
             raise ValueError(f"clip_temperature must be positive and finite, got {clip_temperature}")
         self.clip_loss, self.clip_temperature = clip_loss, float(clip_temperature)
+        self.vision_d = bool(vision_d)
+        if self.vision_d and not self.clip_grad:
+            raise ValueError("vision_d=True needs clip_grad=True (the head's generator gradient goes through the "
+                             "build's own image-tower backward)")
+        vw = float(vision_weight)
+        if not (vw >= 0.0 and vw != float("inf")):
+            raise ValueError(f"vision_weight must be finite and >= 0, got {vision_weight}")
+        if int(vision_hidden) != vision_hidden or int(vision_hidden) % 64 or not 64 <= int(vision_hidden) <= 512:
+            raise ValueError(f"vision_hidden must be a multiple of 64 in [64, 512], got {vision_hidden}")
+        self.vision_weight, self.vision_hidden = vw, int(vision_hidden)
         # exponential moving average of the generator (this build's extension): half-life in optimizer steps, None =
         # off (the reference's step); ema_rampup caps the half-life at ema_rampup * step early on (None / 0: constant)
         if ema_halflife is not None and not ema_halflife > 0:
@@ -129,7 +158,8 @@ def clip_tower(encoder):
 
 
 class TrainStep:
-    def __init__(self, cfg, device="cuda", process_group=None, gstore=None, dstore=None, clip_encoder=None):
+    def __init__(self, cfg, device="cuda", process_group=None, gstore=None, dstore=None, clip_encoder=None,
+                 vstore=None):
         self.cfg = cfg
         self.dev = torch.device(device)
         if getattr(cfg, "deterministic", False):
@@ -156,6 +186,12 @@ class TrainStep:
                 raise ValueError(f"clip_grad=True trains {self.ge.rgb_half[:-1]}, which this parameter store keeps "
                                  "frozen: build it with layout.frozen_rgb_prefixes(max_res, clip_grad=True)")
             self._clip_scale = torch.ones(1, device=self.dev)  # device scalar of mg_cos_loss (the weights ride alpha)
+        # the vision-aided head (cfg.vision_d): a plain store -- no frozen tail, no shadow, no moving average -- sized
+        # by the tower's feature width once one is attached (a given ``vstore`` fixes it)
+        self.vision_d = bool(getattr(cfg, "vision_d", False))
+        self.vs = vstore
+        if self.vision_d:
+            self._vis_scale = torch.full((1,), float(cfg.vision_weight), device=self.dev)
         # optional image encoder for the CLIP loss terms (gradient-free unless cfg.clip_grad); images are
         # [B,3,H,W] in [-1, 1]
         self.clip_encoder = clip_encoder
@@ -173,6 +209,19 @@ class TrainStep:
             raise ValueError("clip_grad=True needs the build's image tower (moegan_mi.clip_vit.ClipImageEncoder or "
                              f"its encode_image) as clip_encoder; {type(enc).__name__} has no backward")
         self._clip_encoder = enc
+        if self.vision_d and self._clip_tower is not None:
+            C = int(self._clip_tower.output_dim)
+            if self.vs is None:
+                from .init import init_vision_head
+                self.vs = ParamStore(vision_head_shapes(C, self.cfg.vision_hidden), self.dev)
+                init_vision_head(self.vs)
+            elif self.vs.shapes["fc.weight"][1] != C:
+                raise ValueError(f"the vision head reads {self.vs.shapes['fc.weight'][1]}-wide features, the tower "
+                                 f"gives {C}")
+
+    def _vhead(self, buf):
+        """The head's six tensors (ops.VHEAD_KEYS) as views into one of ``vs``'s flat buffers."""
+        return {k: self.vs._v(buf, k) for k in ops.VHEAD_KEYS}
 
     # ---- data-parallel reductions ----
     # (collectives stay eager segments when the step is replayed as hipGraphs, graphs.py)
@@ -372,6 +421,7 @@ class TrainStep:
         aug_g = dict(aug_fake=aug[2], aug_mask=aug_mask) if aug is not None else {}
         accum = acc > 1
         gs, ds = self.gs, self.ds
+        vs = self.vs if self.vision_d else None
         flags = ops.zeros(1, device=self.dev, dtype=torch.int32)  # the step's guard word (zero arena)
         self.ge.guard_flags = flags
         if prep:
@@ -382,9 +432,15 @@ class TrainStep:
             ds.ensure_acc()
             if zero_grads:
                 ds.acc.zero_()
+            if vs is not None:
+                vs.ensure_acc()
+                if zero_grads:
+                    vs.acc.zero_()
         # ------------------------- D phase -------------------------
         if zero_grads or accum:
             ds.zero_grad()
+            if vs is not None:
+                vs.zero_grad()
         # the router-independent prefix of this forward (mapping, styles, gen_block_4's convolution block) is
         # kept with its saved activations and reused by the G-phase forward: same z / text, G not yet updated
         f16, _, _, probs_d, topi_d, _ = self.ge.forward(z, text, eps_d, anneal, c.psi, train=True, save=False,
@@ -394,11 +450,23 @@ class TrainStep:
         dres = self.de.d_phase(real, text, f16, ("nhwc", 8), perm, c.r1_gamma, **aug_d)
         ops.fold_flush()
         ops.COLSUMS.flush()
+        vis = None
+        if vs is not None:
+            # the vision-aided head: real batch and D-phase fakes through the frozen tower in one forward-only pass
+            # (un-augmented), then the head's three terms and its parameter gradients
+            B = real.shape[0]
+            real_nhwc = torch.zeros(B, real.shape[2], real.shape[3], 8, device=self.dev, dtype=torch.float32)
+            real_nhwc[..., :3] = real.float().permute(0, 2, 3, 1)
+            vfeats = self._clip_tower.encode_generated([real_nhwc, f16]).float()
+            vis = ops.vhead_d(vfeats[:B], vfeats[B:], text.float().contiguous(), perm, self._vhead(vs.data),
+                              self._vhead(vs.grad))
         # guard: NaN / Inf d_loss skips the whole batch (t2i_moe_gan.py:1315-1320)
-        self._guard(flags, [(dres["losses"][:1], FD), (dres["r1"], FD)],
+        self._guard(flags, [(dres["losses"][:1], FD), (dres["r1"], FD)] + ([(vis[0][:1], FD)] if vis else []),
                     [dict(reset_bits=ops.WIN_D if zero_grads else 0, bad_mask=FD, set_bits=ops.WIN_D)])
         if accum:
             ops.gated_axpy(ds.acc, ds.grad, flags, FD)
+            if vs is not None:
+                ops.gated_axpy(vs.acc, vs.grad, flags, FD)
         dgrad = ds.acc if accum else ds.grad
         d_sumsq = None
         if step_optim:
@@ -406,6 +474,11 @@ class TrainStep:
             d_sumsq = self._adamw(ds, dgrad, lr_d, c.d_clip, flags, [(0, ds.n_opt, ds.step_dev, ops.WIN_D)],
                                   grad_scale=1.0 / acc)
             self.de.prep()
+            if vs is not None:
+                vgrad = vs.acc if accum else vs.grad
+                self._allreduce_mean(vgrad)
+                self._adamw(vs, vgrad, lr_d, c.d_clip, flags, [(0, vs.n_opt, vs.step_dev, ops.WIN_D)],
+                            grad_scale=1.0 / acc)
         # ------------------------- G phase -------------------------
         if accum:
             gs.zero_grad()
@@ -428,7 +501,11 @@ class TrainStep:
         load = ops.zeros(c.E, device=self.dev)
         ops.colsum(last, load)
         self._allreduce_sum(load)
-        bal = torch.empty(1, device=self.dev)  # (mg_balance writes it)
+        if vs is not None:  # the balance term and the head's L_g side by side: one finite check covers both
+            bal_vis = torch.empty(2, device=self.dev)
+            bal, vis_g = bal_vis[:1], bal_vis[1:]
+        else:
+            bal, vis_g = torch.empty(1, device=self.dev), None  # (mg_balance writes it)
         coef = torch.empty(c.E, device=self.dev)
         ops.balance(load, c.E, last.shape[0] * self.world, c.balance_weight, float(self.world), bal, coef)
         # CLIP terms (t2i_moe_gan.py:1385-1387).  Default (the reference): forward only, they enter g_loss's value
@@ -451,7 +528,14 @@ class TrainStep:
                     term, g_f = ops.clip_contrast(feats, t_all, c.clip_temperature, self._clip_scale, pos_off=pos_off)
                 else:
                     term, g_f = ops.cos_loss(feats, t32, self._clip_scale)
-                tower.backward(cctx, g_f, g_out, alpha=w, accumulate=acc_)
+                if vs is not None and img is img16:
+                    # the head as this step's D phase left it; alpha scales the whole feature gradient and
+                    # clip_weight_16 may be 0, so the two gradients are combined in fp32 first
+                    _, _, g_vis = ops.vhead_g(feats, t32, self._vhead(vs.data), self._vis_scale, loss=vis_g)
+                    g_f = torch.add(g_vis, g_f, alpha=float(w))
+                    tower.backward(cctx, g_f, g_out, alpha=1.0, accumulate=acc_)
+                else:
+                    tower.backward(cctx, g_f, g_out, alpha=w, accumulate=acc_)
                 terms.append(term)
                 cctx = None
             clip16, clip8 = terms
@@ -465,7 +549,7 @@ class TrainStep:
         kl_total = torch.empty(1, device=self.dev)
         ops.kl_coefs(kl2, len(kl2s), eff_kl_weight, kl_coef, kl_total)
         # guard: NaN / Inf (GAN + CLIP + balance) generator loss -> 0, the KL term stays (:1396-1404)
-        self._guard(flags, [(t, FG) for t in (g_gan, bal, clip16, clip8) if t is not None],
+        self._guard(flags, [(t, FG) for t in (g_gan, bal if vs is None else bal_vis, clip16, clip8) if t is not None],
                     [dict(reset_bits=(ops.WIN_G_MAIN | ops.WIN_G_KL) if zero_grads else 0, keep_mask=FD, bad_mask=FD,
                           set_bits=ops.WIN_G_KL),
                      dict(bad_mask=FD | FG, set_bits=ops.WIN_G_MAIN)])
@@ -503,4 +587,7 @@ class TrainStep:
                    fake_pred=dres["fake_pred"], mism_pred=dres["mism_pred"], r1_grad=dres["r1_grad"],
                    img16=img16, img8=img8, probs=probs, topi=topi_g, probs_d=probs_d, topi_d=topi_d,
                    fake_img_d=f16, flags=flags, clip16=clip16, clip8=clip8, d_grad=dgrad, g_grad=ggrad)
+        if vs is not None:
+            out.update(vis_d=vis[0], vis_real_pred=vis[1], vis_mism_pred=vis[2], vis_fake_pred=vis[3], vis_g=vis_g,
+                       fake_d=f16, v_grad=vs.acc if accum else vs.grad)
         return out

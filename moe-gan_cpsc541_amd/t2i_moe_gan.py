@@ -35,9 +35,9 @@ if _HERE not in sys.path:
 
 from moegan_mi.engine_d import DiscriminatorEngine  # noqa: E402
 from moegan_mi.engine_g import GeneratorEngine  # noqa: E402
-from moegan_mi.init import init_discriminator, init_generator  # noqa: E402
+from moegan_mi.init import init_discriminator, init_generator, init_vision_head  # noqa: E402
 from moegan_mi.layout import (MAX_RESOLUTIONS, discriminator_shapes, frozen_rgb_prefixes,  # noqa: E402
-                             generator_shapes)
+                             generator_shapes, vision_head_shapes)
 from moegan_mi.params import ParamStore  # noqa: E402
 from moegan_mi.prefetch import DevicePrefetcher  # noqa: E402
 from moegan_mi.step import StepConfig, TrainStep  # noqa: E402
@@ -360,6 +360,30 @@ class AuroraDiscriminator(_FlatModule):
         return _DiscFn.apply(self.flat, img, text_embedding, self)
 
 
+class VisionAidedDiscriminator(_FlatModule):
+    """Vision-aided discriminator head (this build's extension, no reference counterpart; Kumari et al., "Ensembling
+    off-the-shelf models for GAN training"; GigaGAN's L_vision; StyleGAN-T): a conditional head on the features of a
+    frozen image tower.  With x~ / c~ the feature / caption rows scaled to norm sqrt(feature_dim),
+        h = LeakyReLU_0.2(fc x~),  logit = out h + <h, text_proj c~> / sqrt(hidden)
+    (include/moegan_hip.h: mg_vhead_logits; a row whose norm is zero or not finite gives logit 0).  ``forward`` is
+    forward only; training runs inside the fused step (``train_aurora_gan(..., clip_grad=True, vision_d=True)``,
+    StepConfig.vision_d), which owns the gradients.  ``hidden`` = 256 and the initialisation (init_vision_head) are
+    choices.  state_dict keys: fc.weight, fc.bias, text_proj.weight, text_proj.bias, out.weight, out.bias."""
+
+    def __init__(self, feature_dim=512, hidden=256, seed=2):
+        super().__init__(vision_head_shapes(feature_dim, hidden), dtype="fp32")
+        self.feature_dim, self.hidden = int(feature_dim), int(hidden)
+        init_vision_head(self._store, seed)
+
+    @torch.no_grad()
+    def forward(self, features, text_embedding):
+        """features [B, feature_dim] (the tower's image features), text_embedding [B, feature_dim] -> logits [B]."""
+        self._require_gpu()
+        from moegan_mi import ops
+        params = {k: self._store.view(k) for k in ops.VHEAD_KEYS}
+        return ops.vhead_logits(features.float(), text_embedding.float(), params)
+
+
 def encode_text_with_clip(text, model=None):
     model = model or get_clip_model()[0]
     if isinstance(text, str):
@@ -609,11 +633,11 @@ class _NoEvent:
 _STAT_KEYS = ("flags", "d_losses", "r1", "g_gan", "balance", "kl", "clip16", "clip8")
 
 
-def _stats_to_host(out):
+def _stats_to_host(out, keys=_STAT_KEYS):
     """The step's guard word and logged losses as one asynchronous copy into pinned host memory (read after the
     NEXT batch is enqueued, so the host never waits for the batch it just launched)."""
     vals = [out["flags"][:1].float()] + [out[k].reshape(-1)[:1].float() if out.get(k) is not None
-                                         else torch.zeros(1, device=out["flags"].device) for k in _STAT_KEYS[1:]]
+                                         else torch.zeros(1, device=out["flags"].device) for k in keys[1:]]
     dev_vec = torch.cat(vals)
     host = torch.empty(dev_vec.shape, dtype=torch.float32, pin_memory=True)
     host.copy_(dev_vec, non_blocking=True)
@@ -632,7 +656,7 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
                      use_graphs=True, on_batch_done=None, text_tokens=False, max_text_tokens=None, clip_grad=False,
                      ema_kimg=None, ema_rampup=0.05, eval_every=None, eval_samples=None, eval_truncation_psi=1.0,
                      eval_nearest_k=None, eval_frechet=False, diffaug=None, clip_contrastive=False,
-                     clip_temperature=0.07):
+                     clip_temperature=0.07, vision_d=False, vision_weight=1.0):
     """Reference :1029-1669.  ``clip_weight_64``/``clip_weight_32`` (the names train_model.py passes,
     SURVEY.md §0) map to the 16x16 / 8x8 CLIP weights.  ``use_amp`` selects bf16 (the MI355X mixed
     precision; the reference's fp16 GradScaler is not needed) unless ``dtype`` is given.
@@ -682,6 +706,12 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
     a training step, real and fake, goes through a random colour / shift / cutout transform whose parameters are
     drawn per batch from the per-rank generator -- only when the feature is on, so the default random streams and
     resume files are unchanged.  Validation, evaluation, sampling and the CLIP terms see un-augmented images.
+    ``vision_d`` (this build's extension; needs ``clip_grad``; off = the loop as it was): a vision-aided
+    discriminator head (VisionAidedDiscriminator, StepConfig.vision_d) judges real and generated images in the frozen
+    tower's feature space next to the reference's discriminator; its generator-side loss enters with
+    ``vision_weight`` (1.0 is a choice, not a measurement).  The logged line and the dict ``metric_callback`` receives
+    gain ``d_vision`` / ``g_vision`` (the last logged batch's head losses); resume files gain ``vision_head`` /
+    ``optimizer_v``.  Validation is unchanged.
     ``resume_from``: a resume checkpoint (:1484-1491 layout, ours or the reference's) to start from;
     ``save_every_epoch``: write that layout after every epoch (the reference's commented-out :1642-1652).
 
@@ -739,6 +769,9 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
     # max_resolution 16 is the reference generator; 32 / 64 / 128 train the progressive extension (layout.py)
     if clip_contrastive and not clip_grad:
         raise ValueError("clip_contrastive=True needs clip_grad=True (the gradient-free terms stay the cosine)")
+    if vision_d and not clip_grad:
+        raise ValueError("vision_d=True needs clip_grad=True (the head's generator gradient goes through the "
+                         "build's own image-tower backward)")
     if clip_grad and _clip_model is None:
         raise RuntimeError("clip_grad=True needs the CLIP image tower: call load_clip_weights(path) first")
     generator =AuroraGenerator(num_experts=num_experts, topk=topk, dtype=dtype, seed=seed,
@@ -750,10 +783,21 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
                      clip_weight_8=clip_weight_8, balance_weight=balance_weight, beta1=beta1, beta2=beta2,
                      max_res=max_resolution, clip_grad=clip_grad, ema_halflife=ema_halflife,
                      ema_rampup=float(ema_rampup) if ema_rampup is not None else None, diffaug=diffaug,
-                     clip_loss="contrastive" if clip_contrastive else "cosine", clip_temperature=clip_temperature)
+                     clip_loss="contrastive" if clip_contrastive else "cosine", clip_temperature=clip_temperature,
+                     vision_d=bool(vision_d), vision_weight=vision_weight)
+    vision_head = None
+    if vision_d:
+        from moegan_mi.step import clip_tower
+        tower = clip_tower(_clip_model)
+        if tower is None:
+            raise ValueError("vision_d=True needs the build's CLIP image tower: call load_clip_weights(path) first")
+        vision_head = VisionAidedDiscriminator(int(tower.output_dim), cfg.vision_hidden, seed=seed + 2).to(device)
     # CLIP terms of the generator loss (logging / guard only unless clip_grad: no gradient, :98-101)
     ts = TrainStep(cfg, device, process_group=process_group, gstore=generator._store, dstore=discriminator._store,
-                   clip_encoder=_clip_model.encode_image if _clip_model is not None else None)
+                   clip_encoder=_clip_model.encode_image if _clip_model is not None else None,
+                   vstore=vision_head._store if vision_head is not None else None)
+    stat_keys = _STAT_KEYS + (("vis_d", "vis_g") if vision_d else ())
+    last_vision = {}
     if rank == 0:
         print(f"Generator parameters: {generator._store.n_opt + (generator._store.total - generator._store.n_opt):,}")
     lrs = _lr_schedule(lr, num_epochs, lr_warmup_epochs)
@@ -764,7 +808,8 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
     start_epoch, step = 0, 0
     if resume_from is not None:  # also continues the z / permutation / router-noise streams when the file has them
         start_epoch, step = load_resume(resume_from, generator, discriminator,
-                                        generators={f"local{rank}": g_local, "shared": g_shared})
+                                        generators={f"local{rank}": g_local, "shared": g_shared},
+                                        vision_head=vision_head)
         print(f"Resumed from {resume_from}: epoch {start_epoch}, step {step}")
     from tqdm import tqdm
     runner = _StepRunner(ts, device, enabled=use_graphs)
@@ -810,6 +855,10 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
                 pbar.set_postfix({"D_loss": f"{d_gan:.3f}", "R1": f"{r1:.3f}", "G_loss": f"{g_gan:.3f}",
                                   "KL": f"{kl:.4f}", "Balance": f"{bal:.4f}", "Clip16": f"{c16:.3f}",
                                   "Clip8": f"{c8:.3f}"})
+                if vision_d:
+                    last_vision.update(d_vision=v[8], g_vision=v[9])
+                    logger.info(f"  Vision head: D_vision: {v[8]:.4f}, G_vision: {v[9]:.4f} "
+                                f"(weight {float(vision_weight):g})")
             step += 1
         for batch_idx, batch in enumerate(pbar):
             real, text = batch[0], batch[1]
@@ -839,10 +888,10 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
             out = runner(real, text, z, eps_d, eps_g, perm, anneal=temperature_factor, lr_g=cur_lr, lr_d=cur_lr,
                          eff_kl_weight=eff_kl, acc=acc, zero_grads=zero, step_optim=stp, **tok_kw, **aug_kw)
             if device.type == "cuda":
-                rec = _stats_to_host(out) + (batch_idx,)
+                rec = _stats_to_host(out, stat_keys) + (batch_idx,)
             else:
                 rec = (torch.stack([out[k].reshape(-1)[0].float() if out.get(k) is not None else torch.zeros(())
-                                    for k in _STAT_KEYS]), _NoEvent(), batch_idx)
+                                    for k in stat_keys]), _NoEvent(), batch_idx)
             if pending is not None:
                 account(pending)  # the previous batch, now that this one is enqueued
             pending = rec
@@ -872,6 +921,7 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
                 if rank == 0:
                     print(f"Evaluation ({'EMA' if generator._store.ema is not None else 'live'} generator) - "
                           f"{format_metrics(em)}")
+            vm.update(last_vision)
             stop = False
             if rank == 0:
                 print(f"Validation Results - D_loss: {vm['val_d_loss']:.4f}, G_loss: {vm['val_g_loss']:.4f}, "
@@ -885,7 +935,7 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
             stop = False
         if save_every_epoch:  # after validation (which draws from g_local), every rank's local stream
             _save_epoch(save_dir, generator, discriminator, epoch, step, cur_lr, (beta1, beta2), g_local, g_shared,
-                        process_group, rank)
+                        process_group, rank, vision_head=vision_head)
         if stop:
             if rank == 0:
                 print("Early stopping triggered by metric callback")
@@ -894,7 +944,7 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
 
 
 def _save_epoch(save_dir, generator, discriminator, epoch, step, cur_lr, betas, g_local, g_shared, process_group,
-                rank):
+                rank, vision_head=None):
     """End-of-epoch resume file (the reference's commented-out :1642-1652 layout, 'epoch' = epoch + 1), written by
     rank 0 with every rank's local generator state (``rng/local<r>``) gathered over the process group."""
     states = {f"local{rank}": g_local.get_state()}
@@ -906,7 +956,8 @@ def _save_epoch(save_dir, generator, discriminator, epoch, step, cur_lr, betas, 
     if rank == 0:
         states["shared"] = g_shared.get_state()
         save_resume(os.path.join(save_dir, f"aurora_checkpoint_epoch_{epoch + 1}.pt"), generator, discriminator,
-                    epoch, step, cur_lr, cur_lr, betas, epoch_complete=True, generators=states)
+                    epoch, step, cur_lr, cur_lr, betas, epoch_complete=True, generators=states,
+                    vision_head=vision_head)
 
 
 def _validate(generator, discriminator, loader, gan_loss, temperature_factor, eff_kl, device, process_group=None,

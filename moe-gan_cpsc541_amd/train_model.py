@@ -96,6 +96,11 @@ def parse_args(argv=None):
                         "image's own caption the positive) instead of 1 - cos")
     p.add_argument("--clip_temperature", type=float, default=0.07,
                    help="with --clip_contrastive: the softmax temperature (default: CLIP's initial 0.07)")
+    p.add_argument("--vision_d", action="store_true",
+                   help="with --clip_grad: a vision-aided discriminator head judges real and generated images in "
+                        "the frozen CLIP image tower's feature space (default: off)")
+    p.add_argument("--vision_weight", type=float, default=1.0,
+                   help="with --vision_d: weight of the head's generator-side loss (default 1.0, a choice)")
     p.add_argument("--hyperparameters", type=str, default=None,
                    help="SageMaker-style hyperparameters.json (string values, sagemaker_train.py:85-102); batch_size "
                         "and the train_aurora_gan keys override the flags above, other keys are reported as unused")
@@ -139,6 +144,11 @@ def parse_args(argv=None):
         p.error("--clip_contrastive needs --clip_grad (it replaces the term whose gradient trains the generator)")
     if not args.clip_temperature > 0 or args.clip_temperature == float("inf"):
         p.error("--clip_temperature must be positive and finite")
+    if args.vision_d and not args.clip_grad:
+        p.error("--vision_d needs --clip_weights ... --clip_grad (the head's generator gradient goes through the "
+                "image tower's backward)")
+    if not args.vision_weight >= 0 or args.vision_weight == float("inf"):
+        p.error("--vision_weight must be finite and >= 0")
     if args.eval_every and not args.clip_weights:
         p.error("--eval_every needs --clip_weights (the CLIP image tower whose features it compares)")
     if args.eval_nearest_k is not None and not args.eval_every:
@@ -225,6 +235,9 @@ def main(argv=None):
     if args.clip_contrastive:
         kw.setdefault("clip_contrastive", True)
         kw.setdefault("clip_temperature", args.clip_temperature)
+    if args.vision_d:
+        kw.setdefault("vision_d", True)
+        kw.setdefault("vision_weight", args.vision_weight)
     if args.ema_kimg is not None:
         kw.setdefault("ema_kimg", args.ema_kimg)
         kw.setdefault("ema_rampup", args.ema_rampup)
