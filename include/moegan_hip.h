@@ -385,6 +385,16 @@ int mg_attn_fwd(int dtype, const void* qkv, int B, int L, int C, int heads, void
 /* Self-attention backward -> gqkv [B*L, 3C]. */
 int mg_attn_bwd(int dtype, int gout_dtype, const void* qkv, const void* out, const void* gout, const float* lse, int B, int L, int C, int heads, void* gqkv, void* stream);
 
+/* Long-sequence self-attention (the AttentionBlock of gen_block_32): the contract of mg_attn_fwd / mg_attn_bwd for
+   256 < L <= 1024, L a multiple of 64, 8 heads of head dim 16 (C = 128); anything else is refused with MG_ERR_ARG
+   before any launch.  Keys are walked in tiles with an online softmax: no L x L matrix, registers independent of L.
+   bf16 runs on MFMA with a head's K / V (or Q / dO) staged in LDS, fp32 on key-tiled scalar kernels.  The backward
+   takes gout in the dtype of qkv, keeps delta and lse (2 B heads L floats) in the stream's workspace, and has one
+   writer per gqkv element: no atomics, bit-reproducible, graph-capturable once the workspace is reserved. */
+int mg_attn_long_fwd(int dtype, const void* qkv, int B, int L, int C, int heads, void* out, float* lse, void* stream);
+
+int mg_attn_long_bwd(int dtype, int gout_dtype, const void* qkv, const void* out, const void* gout, const float* lse, int B, int L, int C, int heads, void* gqkv, void* stream);
+
 /* Ragged causal self-attention forward (CLIP text tower): qkv [R, 3C] (q | k | v), sequence b = rows row_off[b] .. row_off[b+1]-1 (row_off device int32 [B+1], 1 <= length <= Lmax <= 128), query i attends to keys j <= i of its sequence; out [R, C]. bf16 with head dim 64 runs on MFMA, fp32 and other head dims (16 / 32) on a scalar kernel; no atomics, bit-reproducible. */
 int mg_attn_causal_fwd(int dtype, const void* qkv, const int32_t* row_off, int B, int Lmax, int C, int heads, void* out, void* stream);
 
@@ -548,7 +558,7 @@ int mg_moe_gate_grad(int dtype, int gout_dtype, const void* gout, int64_t ldg, c
 
 /* Router backward per token -> g_raw [T,E], per-image sums gsum [B,E] (written), temperature grad (+=; per-block
    partials in the stream's workspace, folded in a fixed order: bit-identical run to run).  HW (tokens per image) a
-   power of two <= 256.  Upstream gradients (each optional): g_gate (combine weights), g_probs + coef[e]
+   power of two <= 1024 (above 256, with T a multiple of HW: one block per image, the <= 256 kernels untouched).  Upstream gradients (each optional): g_gate (combine weights), g_probs + coef[e]
    (probabilities), g_logits (the clamped logits, the router's second output).  Reference :374-389. */
 int mg_router_bwd(const float* probs, const float* zlog, const int32_t* topi, const float* gate, const float* g_gate, const float* g_probs, const float* g_logits, const float* coef, int T, int E, int k, int HW, const float* temperature, float anneal, float* g_raw, float* gsum, float* g_temp, void* stream);
 

@@ -903,6 +903,127 @@ __global__ __launch_bounds__(256) void k_router_bwd(const float* __restrict__ pr
 }
 
 
+// k_router_bwd for images of 512 / 1024 tokens (HW > 256: gen_block_32's router), the same per-token math: one block of
+// 256 threads per image, thread i taking tokens i, i + 256, ... in turn and keeping its share of the image's sums in
+// registers; the shares are folded by a wave butterfly and the block's four waves in wave order, the temperature
+// partial alike -- one writer per gsum element and per block partial, a fixed order, no atomics.
+template <int E>
+__global__ __launch_bounds__(256) void k_router_bwd_wide(const float* __restrict__ probs, const float* __restrict__ zlog,
+                                                         const int* __restrict__ topi, const float* __restrict__ gate,
+                                                         const float* __restrict__ g_gate,
+                                                         const float* __restrict__ g_probs,
+                                                         const float* __restrict__ g_logits,
+                                                         const float* __restrict__ coef, int Tn, int k, int lgHW,
+                                                         const float* __restrict__ temp, float anneal,
+                                                         float* __restrict__ g_raw, float* __restrict__ gsum,
+                                                         float* __restrict__ tpart) {
+  __shared__ float red[4 * E];
+  __shared__ float tred[4];
+  const int HW = 1 << lgHW, t0 = blockIdx.x << lgHW;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float te = teff_of(temp, anneal);
+  float gt_part = 0.f;
+  float grv[E];
+#pragma unroll
+  for (int e = 0; e < E; ++e) grv[e] = 0.f;
+  for (int tt = threadIdx.x; tt < HW; tt += 256) {
+    const int t = t0 + tt;
+    if (t >= Tn) break;
+    float p[E], gp[E], z[E];
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      p[e] = probs[(int64_t)t * E + e];
+      z[e] = zlog[(int64_t)t * E + e];
+      gp[e] = (coef ? coef[e] : 0.f) + (g_probs ? g_probs[(int64_t)t * E + e] : 0.f);
+    }
+    if (g_gate) {
+      if (k == E) {
+        for (int j = 0; j < k; ++j) {
+          int ex = topi[(int64_t)t * k + j];
+#pragma unroll
+          for (int e = 0; e < E; ++e)
+            if (e == ex) gp[e] += g_gate[(int64_t)t * k + j];
+        }
+      } else {
+        float S = 0.f, dot = 0.f;
+        for (int j = 0; j < k; ++j) {
+          int ex = topi[(int64_t)t * k + j];
+#pragma unroll
+          for (int e = 0; e < E; ++e)
+            if (e == ex) S += p[e];
+          dot += g_gate[(int64_t)t * k + j] * gate[(int64_t)t * k + j];
+        }
+        for (int j = 0; j < k; ++j) {
+          int ex = topi[(int64_t)t * k + j];
+          float v = (g_gate[(int64_t)t * k + j] - dot) / S;
+#pragma unroll
+          for (int e = 0; e < E; ++e)
+            if (e == ex) gp[e] += v;
+        }
+      }
+    }
+    // recompute softmax s and clamped q
+    float l[E], s[E], q[E];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      l[e] = fminf(fmaxf(z[e], -20.f), 20.f);
+      mx = fmaxf(mx, l[e]);
+    }
+    float den = 0.f;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      s[e] = expf(l[e] - mx);
+      den += s[e];
+    }
+    float Sq = 0.f;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      s[e] /= den;
+      q[e] = fminf(fmaxf(s[e], 1e-6f), 1.f);
+      Sq += q[e];
+    }
+    float d1 = 0.f;  // p = q / Sq
+#pragma unroll
+    for (int e = 0; e < E; ++e) d1 += gp[e] * (q[e] / Sq);
+    float gs_[E];
+    float d2 = 0.f;
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      float gq = (gp[e] - d1) / Sq;
+      gs_[e] = (s[e] >= 1e-6f && s[e] <= 1.f) ? gq : 0.f;
+      d2 += gs_[e] * s[e];
+    }
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      float gl = s[e] * (gs_[e] - d2);
+      if (g_logits) gl += g_logits[(int64_t)t * E + e];  // the router's second output, logits (:378-381)
+      gl = (z[e] >= -20.f && z[e] <= 20.f) ? gl : 0.f;
+      gt_part += -gl * z[e] / te;
+      const float gr = gl / te;
+      grv[e] += gr;
+      g_raw[(int64_t)t * E + e] = gr;
+    }
+  }
+#pragma unroll
+  for (int e = 0; e < E; ++e) {
+    grv[e] = wave_sum(grv[e]);
+    if (lane == 0) red[wave * E + e] = grv[e];
+  }
+  gt_part = wave_sum(gt_part);
+  if (lane == 0) tred[wave] = gt_part;
+  __syncthreads();
+  if (threadIdx.x < E && t0 < Tn) {
+    const int e = threadIdx.x;
+    gsum[(int64_t)blockIdx.x * E + e] = ((red[e] + red[E + e]) + red[2 * E + e]) + red[3 * E + e];
+  }
+  if (threadIdx.x == 0 && tpart) {
+    const float tt = ((tred[0] + tred[1]) + tred[2]) + tred[3];
+    const float raw = temp[0] * anneal;
+    tpart[blockIdx.x] = (raw >= 0.5f && raw <= 5.f) ? tt * anneal : 0.f;
+  }
+}
+
 MG_DEV float team_sum(float v) {
   v += __shfl_xor(v, 1, 64);
   v += __shfl_xor(v, 2, 64);
@@ -1732,10 +1853,27 @@ extern "C" int mg_router_bwd(const float* probs, const float* zlog, const int32_
                              const float* temperature, float anneal, float* g_raw, float* gsum, float* g_temp,
                              void* stream) {
   MG_REQUIRE(E == 4 || E == 8 || E == 16 || E == 32, "E must be 4, 8, 16 or 32");
-  MG_REQUIRE(HW >= 1 && HW <= 256 && (HW & (HW - 1)) == 0, "HW must be a power of two <= 256");
+  MG_REQUIRE(HW >= 1 && HW <= 1024 && (HW & (HW - 1)) == 0, "HW must be a power of two <= 1024");
   hipStream_t st = reinterpret_cast<hipStream_t>(stream);
   int lg = 0;
   while ((1 << lg) < HW) ++lg;
+  if (HW > 256) {  // 512 / 1024 tokens per image: one block per image (k_router_bwd_wide); HW <= 256 is untouched below
+    MG_REQUIRE(T >= 0 && T % HW == 0, "T must be a multiple of HW");
+    if (T == 0) return MG_OK;
+    dim3 gw(T / HW);
+    float* tp = nullptr;
+    bool dfr = false;
+    if (g_temp) {
+      tp = mg_fold_partials((size_t)gw.x * sizeof(float), st, &dfr);
+      if (!tp) return MG_ERR_LAUNCH;
+    }
+#define LW_(EE) hipLaunchKernelGGL(k_router_bwd_wide<EE>, gw, dim3(256), 0, st, probs, zlog, topi, gate, g_gate, g_probs, \
+                                   g_logits, coef, T, k, lg, temperature, anneal, g_raw, gsum, tp)
+    if (E == 4) LW_(4); else if (E == 8) LW_(8); else if (E == 16) LW_(16); else LW_(32);
+#undef LW_
+    if (g_temp) mg_fold_rows_submit(mg_fold_rows{tp, 1, (int)gw.x, 1, 1, g_temp, nullptr}, dfr, st);
+    return mg_check_launch("mg_router_bwd");
+  }
   const bool team = E >= 8 && (g_mg_tune[MG_TUNE_ROUTER_TEAM] & 2) == 0;
   const int nteam = HW >= 128 ? 128 : HW >= 64 ? 64 : 32;  // teams per block
   dim3 grid(team ? cdiv(T, std::max(HW, nteam)) : cdiv(T, 256));

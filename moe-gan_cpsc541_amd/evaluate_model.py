@@ -55,6 +55,8 @@ def parse_args(argv=None):
     p.add_argument("--topk", type=int, default=None, help="sparse top-k routing (default: dense soft combine)")
     p.add_argument("--dtype", choices=["fp32", "bf16"], default="fp32")
     p.add_argument("--max_resolution", type=int, default=16, choices=[16, 32, 64, 128])
+    p.add_argument("--attn_resolution", type=int, default=None, choices=[16, 32],
+                   help="the attn_resolution the checkpoint was trained with (default: read from its keys)")
     args = p.parse_args(argv)
     if not 1 <= args.group <= 128:
         p.error("--group must be between 1 and 128")
@@ -75,7 +77,11 @@ def main(argv=None):
     from train_model import ProcessedMSCOCODataset
     device = M.DEVICE
     ck = torch.load(args.checkpoint, map_location="cpu", weights_only=True)
-    generator = M.AuroraGenerator(max_resolution=args.max_resolution, num_experts=args.num_experts, topk=args.topk,
+    if args.attn_resolution is None:  # inferred from the checkpoint's keys (layout.attn_res_of)
+        from moegan_mi.layout import attn_res_of
+        args.attn_resolution = attn_res_of(generator_state(ck, args.ema))
+    generator = M.AuroraGenerator(max_resolution=args.max_resolution, attn_resolution=args.attn_resolution,
+                                  num_experts=args.num_experts, topk=args.topk,
                                   dtype=args.dtype).to(device)
     generator.load_state_dict(generator_state(ck, args.ema))
     M.load_clip_weights(args.clip_weights, device)

@@ -18,16 +18,16 @@ import torch
 
 from . import _lib as L
 from . import graphs, ops
-from .layout import gen_blocks, max_res_of, rgb_layers
+from .layout import attn_res_of, gen_blocks, max_res_of, rgb_layers
 
 E_ = ops.E
 LRELU, GELU, RSQRT = L.ACT_LRELU, L.ACT_GELU, L.ACT_RSQRT_EPS
 MUL_GELU_GRAD, MUL_LRELU_GRAD = L.ACT_MUL_GELU_GRAD, L.ACT_MUL_LRELU_GRAD
 
 
-def _modconv_prefixes(max_res=16):
+def _modconv_prefixes(max_res=16, attn_res=16):
     out = []
-    for name, cin, cout, _, _, attn in gen_blocks(max_res):
+    for name, cin, cout, _, _, attn in gen_blocks(max_res, attn_res):
         cb = name + ".conv_block."
         out += [(cb + "mtm1.modulated_conv.", 3), (cb + "mtm2.modulated_conv.", 3)]
         if cin != cout:
@@ -50,12 +50,13 @@ class GeneratorEngine:
         self.st = store
         # block list: the reference's three blocks, or the progressive extension when the store holds it
         self.max_res = max_res_of(store.offsets)
-        self.blocks = gen_blocks(self.max_res)
+        self.attn_res = attn_res_of(store.offsets)
+        self.blocks = gen_blocks(self.max_res, self.attn_res)
         self.attn_blocks = [b[0] for b in self.blocks if b[5]]
         rgb = rgb_layers(self.max_res)
         self.rgb_final, self.rgb_half = rgb[-1][0] + ".", rgb[-2][0] + "."
         self.half_block = "gen_block_%d" % (self.max_res // 2)
-        self.mc_list = _modconv_prefixes(self.max_res) if modconvs is None else list(modconvs)
+        self.mc_list = _modconv_prefixes(self.max_res, self.attn_res) if modconvs is None else list(modconvs)
         self.off_list = _offset_prefixes(self.max_res) if offset_nets is None else list(offset_nets)
         self.E = E
         self.k = topk or E

@@ -15,7 +15,7 @@ import json
 
 # sagemaker_train.py:94-99
 INT_KEYS = ("batch_size", "epochs", "kl_annealing_epochs", "lr_warmup_epochs", "eval_every", "eval_samples",
-            "eval_nearest_k")
+            "eval_nearest_k", "attn_resolution")
 FLOAT_KEYS = ("learning_rate", "beta1", "beta2", "r1_gamma", "clip_weight_16", "clip_weight_8", "kl_weight",
               "balance_weight", "ema_kimg", "ema_rampup", "clip_temperature", "vision_weight")
 # this build's switches: "true" / "1" / "yes" / "on" (any case) turn one on, "false" / "0" / "no" / "off" / "" off
@@ -61,6 +61,9 @@ TRAIN_KWARGS = {
     # its generator-side loss weighted by vision_weight (1.0: a choice, not a measurement); off unless set
     "vision_d": ("vision_d", False),
     "vision_weight": ("vision_weight", 1.0),
+    # this build's extension: the finest generator block with an AttentionBlock; 32 (with a max_resolution >= 32)
+    # adds one to gen_block_32.  16 = the reference
+    "attn_resolution": ("attn_resolution", 16),
 }
 # fixed by the SageMaker entry point (sagemaker_train.py:287-292)
 TRAIN_FIXED = {"log_interval": 100, "save_interval": 500, "gradient_accumulation_steps": 8,

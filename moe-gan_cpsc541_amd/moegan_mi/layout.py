@@ -17,20 +17,34 @@ GEN_BLOCKS = (("gen_block_4", 512, 512, 4, False),
               ("gen_block_16", 256, 128, 16, True))
 # Progressive extension (BASELINE config C4): the reference names gen_block_32 / _64 and
 # to_rgb_32 / _64 only in dead code (create_optimizer_for_active_blocks, t2i_moe_gan.py:1005-1026) and defines
-# none of them.  The build's extension blocks are GenerativeBlocks without the attention block: upsample +
-# ConvolutionBlock whose MTMs have no offset head (the reference's own rule, offsets only at resolution <= 16,
-# :199).  Self-attention over (2^r)^2 tokens per image would cost 4 L^2 C flops -- at 128^2 more than the rest of
-# the step -- so the MoE / attention stays at 4 / 8 / 16.  (name, Cin, Cout, resolution)
+# none of them.  The build's extension blocks are GenerativeBlocks whose MTMs have no offset head (the reference's
+# own rule, offsets only at resolution <= 16, :199).  By default they carry no attention block (upsample +
+# ConvolutionBlock): self-attention over (2^r)^2 tokens per image costs 4 L^2 C flops -- at 128^2 more than the rest
+# of the step.  At 32^2 (L = 1024, C = 128: 0.54 GF per image) it is affordable, and ``attn_res=32`` gives
+# gen_block_32 the reference's full AttentionBlock (self-attention on csrc/mg_attn_long.hip); 64^2 / 128^2 never
+# carry one.  (name, Cin, Cout, resolution)
 EXT_BLOCKS = (("gen_block_32", 128, 128, 32), ("gen_block_64", 128, 64, 64), ("gen_block_128", 64, 32, 128))
 MAX_RESOLUTIONS = (16, 32, 64, 128)
+ATTN_RESOLUTIONS = (16, 32)  # the finest block with an AttentionBlock
 
 
-def gen_blocks(max_res=16):
-    """(name, Cin, Cout, resolution, upsample, attention) of every generator block up to ``max_res``."""
+def check_attn_res(max_res, attn_res):
+    """Validate the ``attn_res`` / ``attn_resolution`` option against ``max_res``; returns attn_res."""
+    if attn_res not in ATTN_RESOLUTIONS:
+        raise ValueError(f"attn_resolution must be one of {ATTN_RESOLUTIONS}, got {attn_res}")
+    if attn_res > max_res:
+        raise ValueError(f"attn_resolution {attn_res} needs max_resolution >= {attn_res}, got {max_res}")
+    return attn_res
+
+
+def gen_blocks(max_res=16, attn_res=16):
+    """(name, Cin, Cout, resolution, upsample, attention) of every generator block up to ``max_res``; blocks up to
+    ``attn_res`` (16: the reference's three; 32: gen_block_32 too) carry an AttentionBlock."""
     if max_res not in MAX_RESOLUTIONS:
         raise ValueError(f"max_resolution must be one of {MAX_RESOLUTIONS}, got {max_res}")
+    check_attn_res(max_res, attn_res)
     out = [b + (True,) for b in GEN_BLOCKS]
-    out += [(n, ci, co, r, True, False) for n, ci, co, r in EXT_BLOCKS if r <= max_res]
+    out += [(n, ci, co, r, True, r <= attn_res) for n, ci, co, r in EXT_BLOCKS if r <= max_res]
     return tuple(out)
 
 
@@ -43,6 +57,13 @@ def rgb_layers(max_res=16):
 def max_res_of(shapes):
     """The generator resolution a state_dict / shape table describes."""
     return max(r for r in MAX_RESOLUTIONS if r == 16 or f"to_rgb_{r}.weight" in shapes)
+
+
+def attn_res_of(shapes):
+    """The finest resolution whose block carries an AttentionBlock in a state_dict / shape table."""
+    return max(r for r in ATTN_RESOLUTIONS if r == 16 or f"gen_block_{r}.attn_block.norm1.weight" in shapes)
+
+
 BUFFER_SUFFIXES = ("epsilon_f", "epsilon_t", "epsilon_c")
 
 
@@ -98,9 +119,10 @@ def _attn(d, pre, c, E):
     _modconv(d, pre + "proj_out.", c, c, 1)
 
 
-def generator_shapes(E=4, max_res=16):
+def generator_shapes(E=4, max_res=16, attn_res=16):
     """Ordered ``{state_dict key: shape}`` of AuroraGenerator with E experts (``max_res`` > 16: the progressive
-    extension, gen_blocks)."""
+    extension, gen_blocks; ``attn_res`` = 32: gen_block_32.attn_block.* directly after that block's conv_block.*
+    keys, where a reference GenerativeBlock registers them)."""
     d = OrderedDict()
     d["constant"] = (1, 512, 4, 4)
     for i in (0, 3):
@@ -116,7 +138,7 @@ def generator_shapes(E=4, max_res=16):
     for i in (2, 4, 6):
         d[f"mapping.{i}.weight"] = (512, 512)
         d[f"mapping.{i}.bias"] = (512,)
-    for name, cin, cout, res, _, attn in gen_blocks(max_res):
+    for name, cin, cout, res, _, attn in gen_blocks(max_res, attn_res):
         cb = name + ".conv_block."
         _mtm(d, cb + "mtm1.", cin, cout, res <= 16)
         _mtm(d, cb + "mtm2.", cout, cout, res <= 16)

@@ -845,13 +845,15 @@ def layernorm_bwd(gy, x, mean, rstd, gamma, gx, ggamma, gbeta, accumulate=0):
 def attn_fwd(qkv, B, L, C, heads=8):
     out = torch.empty(B * L, C, device=qkv.device, dtype=qkv.dtype)
     lse = torch.empty(B, heads, L, device=qkv.device, dtype=torch.float32)
-    call("mg_attn_fwd", dt(qkv), ptr(qkv), B, L, C, heads, ptr(out), ptr(lse), S())
+    # L > 256 (gen_block_32's 1024 tokens): the streaming kernels of mg_attn_long.hip
+    call("mg_attn_long_fwd" if L > 256 else "mg_attn_fwd", dt(qkv), ptr(qkv), B, L, C, heads, ptr(out), ptr(lse), S())
     return out, lse
 
 
 def attn_bwd(qkv, out, gout, lse, B, L, C, heads=8):
     gqkv = torch.empty_like(qkv)
-    call("mg_attn_bwd", dt(qkv), dt(gout), ptr(qkv), ptr(out), ptr(gout), ptr(lse), B, L, C, heads, ptr(gqkv), S())
+    call("mg_attn_long_bwd" if L > 256 else "mg_attn_bwd", dt(qkv), dt(gout), ptr(qkv), ptr(out), ptr(gout), ptr(lse),
+         B, L, C, heads, ptr(gqkv), S())
     return gqkv
 
 

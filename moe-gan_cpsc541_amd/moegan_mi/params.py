@@ -252,6 +252,12 @@ class ParamStore:
         missing = [n for n in self.shapes if n not in sd]
         unexpected = [n for n in sd if n not in self.shapes]
         if strict and (missing or unexpected):
+            a32 = "gen_block_32.attn_block."
+            if any(n.startswith(a32) for n in missing) != any(n.startswith(a32) for n in unexpected):
+                have, want = (16, 32) if any(n.startswith(a32) for n in missing) else (32, 16)
+                raise KeyError(f"state_dict mismatch: the checkpoint was written with attn_resolution={have} "
+                               f"(attn_res), this model was built with attn_resolution={want}: rebuild the model "
+                               f"with attn_resolution={have}")
             raise KeyError(f"state_dict mismatch: missing={missing[:5]} unexpected={unexpected[:5]}")
         with torch.no_grad():
             for n, t in sd.items():

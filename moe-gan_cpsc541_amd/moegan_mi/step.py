@@ -70,8 +70,11 @@ class StepConfig:
                  balance_weight=0.01, beta1=0.5, beta2=0.999, weight_decay=0.01, eps=1e-8, d_clip=0.7, g_clip=0.8,
                  psi=0.7, fp8=False, max_res=16, deterministic=None, clip_grad=False, ema_halflife=None,
                  ema_rampup=None, diffaug=None, clip_loss="cosine", clip_temperature=0.07, vision_d=False,
-                 vision_weight=1.0, vision_hidden=256):
-        """``vision_d`` (needs ``clip_grad=True``: the head's generator gradient goes through the build's own tower
+                 vision_weight=1.0, vision_hidden=256, attn_res=16):
+        """``attn_res`` (16 or 32; 32 needs ``max_res`` >= 32): the finest block with an AttentionBlock
+        (layout.gen_blocks); 16 is the reference's generator.
+
+        ``vision_d`` (needs ``clip_grad=True``: the head's generator gradient goes through the build's own tower
         backward): the vision-aided discriminator head of the module docstring, hidden width ``vision_hidden`` (a
         multiple of 64 in [64, 512]; 256 is a choice); its generator-side loss enters with ``vision_weight`` (finite,
         >= 0).  The default 1.0 -- the adversarial term's own weight -- is a choice, not a measurement.
@@ -88,6 +91,8 @@ class StepConfig:
         self.diffaug_mask = None if diffaug is None else parse_policy(diffaug)  # (ValueError for an unknown name)
         # generator output resolution: 16 = the reference; 32 / 64 / 128 = the progressive extension (layout.py)
         self.max_res = max_res
+        from .layout import check_attn_res
+        self.attn_res = check_attn_res(max_res, attn_res)
         self.dtype = dtype
         self.fp8 = fp8  # MX-fp8 3x3 modulated convs (BASELINE config C5), inside the bf16 mode
         self.r1_gamma = r1_gamma
@@ -166,7 +171,7 @@ class TrainStep:
             ops.set_deterministic(True)
         self.cdt = torch.bfloat16 if cfg.dtype == "bf16" else torch.float32
         self.gs = gstore if gstore is not None else ParamStore(
-            generator_shapes(cfg.E, getattr(cfg, "max_res", 16)), self.dev,
+            generator_shapes(cfg.E, getattr(cfg, "max_res", 16), getattr(cfg, "attn_res", 16)), self.dev,
             frozen_prefixes=frozen_rgb_prefixes(getattr(cfg, "max_res", 16), getattr(cfg, "clip_grad", False)),
             shadow_dtype=self.cdt)
         self.ds = dstore if dstore is not None else ParamStore(discriminator_shapes(), self.dev)
@@ -372,8 +377,8 @@ class TrainStep:
     def step(self, real, text, z, eps_d, eps_g, perm, *, anneal=3.0, lr_g=2e-4, lr_d=2e-4, eff_kl_weight=1e-8,
              prep=True, acc=1, zero_grads=True, step_optim=True, text_rows=None, row_off=None, lk_max=None,
              aug=None):
-        """real [B,3,64,64] fp32 NCHW, text [B,512], z [B,512] fp32 (device); eps_d / eps_g: 3 triples of
-        router epsilon tensors; perm [B] int32.  Returns a dict of device tensors.
+        """real [B,3,64,64] fp32 NCHW, text [B,512], z [B,512] fp32 (device); eps_d / eps_g: one triple of
+        router epsilon tensors per attention block (three; four with attn_res = 32); perm [B] int32.  Returns a dict of device tensors.
 
         ``text_rows`` [rows, 512] (pad rows zero) / ``row_off`` device int32 [B+1] / ``lk_max``: per-token text
         features in packed form (tokens.pack_tokens).  The generator's attention blocks then attend over each

@@ -111,7 +111,9 @@ def _eps_for(store, generator=None):
     """Fresh router noise for one generator forward (the reference draws normal_() into its epsilon buffers per
     router, :349-351); ``generator`` = a torch.Generator (the rank-shared one under data parallelism)."""
     eps = []
-    for name in ("gen_block_4", "gen_block_8", "gen_block_16"):  # the attention (MoE) blocks at every max_res
+    # one triple per attention (MoE) block, in block order: three, or four with attn_resolution = 32
+    for name in sorted({n.split(".")[0] for n in store.buffers if n.endswith(".attn_block.moe.router.epsilon_f")},
+                       key=lambda s: int(s.rsplit("_", 1)[1])):
         r = f"{name}.attn_block.moe.router."
         trip = []
         for n in ("epsilon_f", "epsilon_t", "epsilon_c"):
@@ -206,17 +208,19 @@ class AuroraGenerator(_FlatModule):
     """Reference :668-855.  Extra keyword args: num_experts (default 4, as NUM_EXPERTS), topk (None = dense
     soft combine over all experts, as the reference trains), dtype ("fp32" | "bf16").  ``max_resolution`` 16 is
     the reference; 32 / 64 / 128 select the progressive extension (moegan_mi/layout.py gen_blocks: the output is
-    R x R and ``return_intermediate`` gives the R/2 image)."""
+    R x R and ``return_intermediate`` gives the R/2 image).  ``attn_resolution`` 16 is the reference's three attention
+    blocks; 32 (needs ``max_resolution`` >= 32) gives gen_block_32 the full AttentionBlock as well."""
 
     def __init__(self, latent_dim=LATENT_DIM, text_embedding_dim=512, max_resolution=16, num_experts=NUM_EXPERTS,
-                 topk=None, dtype="fp32", seed=0, clip_grad=False):
+                 topk=None, dtype="fp32", seed=0, clip_grad=False, attn_resolution=16):
         if latent_dim != 512 or text_embedding_dim != 512 or max_resolution not in MAX_RESOLUTIONS:
             raise ValueError("the architecture is fixed at latent 512, text 512 and a 16x16 output (the reference) "
                              f"or one of the progressive resolutions {MAX_RESOLUTIONS[1:]}")
         # clip_grad (train_aurora_gan(clip_grad=True)): the half-resolution to_rgb trains, so it is not frozen
-        super().__init__(generator_shapes(num_experts, max_resolution),
+        super().__init__(generator_shapes(num_experts, max_resolution, attn_resolution),
                          frozen=frozen_rgb_prefixes(max_resolution, clip_grad), dtype=dtype)
         self.latent_dim, self.text_embedding_dim, self.max_resolution = latent_dim, text_embedding_dim, max_resolution
+        self.attn_resolution = attn_resolution
         self.num_experts, self.topk = num_experts, topk
         self._use_checkpointing = False
         self._eng = None
@@ -243,7 +247,8 @@ class AuroraGenerator(_FlatModule):
         g = self._ema_gen
         if g is None or g._store.data.data_ptr() != st.ema.data_ptr() or g._store.device != st.ema.device:
             if g is None:
-                g = AuroraGenerator(max_resolution=self.max_resolution, num_experts=self.num_experts, topk=self.topk,
+                g = AuroraGenerator(max_resolution=self.max_resolution, attn_resolution=self.attn_resolution,
+                                    num_experts=self.num_experts, topk=self.topk,
                                     dtype="bf16" if self._cdt == torch.bfloat16 else "fp32",
                                     clip_grad=self._clip_grad)
                 g.requires_grad_(False)
@@ -656,7 +661,7 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
                      use_graphs=True, on_batch_done=None, text_tokens=False, max_text_tokens=None, clip_grad=False,
                      ema_kimg=None, ema_rampup=0.05, eval_every=None, eval_samples=None, eval_truncation_psi=1.0,
                      eval_nearest_k=None, eval_frechet=False, diffaug=None, clip_contrastive=False,
-                     clip_temperature=0.07, vision_d=False, vision_weight=1.0):
+                     clip_temperature=0.07, vision_d=False, vision_weight=1.0, attn_resolution=16):
     """Reference :1029-1669.  ``clip_weight_64``/``clip_weight_32`` (the names train_model.py passes,
     SURVEY.md §0) map to the 16x16 / 8x8 CLIP weights.  ``use_amp`` selects bf16 (the MI355X mixed
     precision; the reference's fp16 GradScaler is not needed) unless ``dtype`` is given.
@@ -775,7 +780,8 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
     if clip_grad and _clip_model is None:
         raise RuntimeError("clip_grad=True needs the CLIP image tower: call load_clip_weights(path) first")
     generator =AuroraGenerator(num_experts=num_experts, topk=topk, dtype=dtype, seed=seed,
-                                max_resolution=max_resolution, clip_grad=clip_grad).to(device)
+                                max_resolution=max_resolution, clip_grad=clip_grad,
+                                attn_resolution=attn_resolution).to(device)
     discriminator = AuroraDiscriminator(dtype=dtype, seed=seed + 1).to(device)
     if checkpoint_activation:
         generator.enable_checkpointing()
@@ -784,7 +790,7 @@ def train_aurora_gan(dataloader, val_dataloader=None, num_epochs=50, lr=0.0002, 
                      max_res=max_resolution, clip_grad=clip_grad, ema_halflife=ema_halflife,
                      ema_rampup=float(ema_rampup) if ema_rampup is not None else None, diffaug=diffaug,
                      clip_loss="contrastive" if clip_contrastive else "cosine", clip_temperature=clip_temperature,
-                     vision_d=bool(vision_d), vision_weight=vision_weight)
+                     vision_d=bool(vision_d), vision_weight=vision_weight, attn_res=attn_resolution)
     vision_head = None
     if vision_d:
         from moegan_mi.step import clip_tower

@@ -86,6 +86,9 @@ def parse_args(argv=None):
     p.add_argument("--save_every_epoch", action="store_true", help="write a resume checkpoint after every epoch")
     p.add_argument("--max_resolution", type=int, default=16, choices=[16, 32, 64, 128],
                    help="generator output size: 16 = the reference; 32/64/128 = the progressive extension")
+    p.add_argument("--attn_resolution", type=int, default=16, choices=[16, 32],
+                   help="finest block with an AttentionBlock: 16 = the reference; 32 (needs --max_resolution >= 32) "
+                        "adds self-attention, text cross-attention and the MoE to gen_block_32")
     p.add_argument("--clip_weights", type=str, default=None,
                    help="local OpenAI CLIP state_dict / safetensors: enables the CLIP loss terms (logged only, "
                         "as in the reference, unless --clip_grad)")
@@ -228,6 +231,7 @@ def main(argv=None):
     if args.clip_weights:
         M.load_clip_weights(args.clip_weights, device)
     kw.setdefault("max_resolution", args.max_resolution)
+    kw.setdefault("attn_resolution", args.attn_resolution)
     if args.text_tokens:
         kw.update(text_tokens=True, max_text_tokens=args.max_text_tokens)
     if args.clip_grad:
