@@ -2,10 +2,13 @@
 //
 // C[m, n] = sum_k A[m, k] * B[k, n], tiles staged through LDS with both
 // operands stored k-contiguous ([rows][BK+pad]) so every lane reads its MFMA
-// fragment with one 16-byte ds_read.  When two LDS stages fit (bf16), the K loop
-// is double-buffered with two register stages: step t+3 is loaded while step t
-// is multiplied, one barrier per K step.  256 threads = 4 waves in a 2x2
+// fragment with one 16-byte ds_read.  256 threads = 4 waves in a 2x2
 // arrangement; each wave owns a (BM/2)x(BN/2) sub-tile of 16x16 fragments.
+// The K loop (gemm_tile) is one of two pipelines, chosen per instantiation:
+//   - LDS-DMA (buffer_load ... lds) into two LDS stages, step t+1 in flight while step t is multiplied, no staging
+//     registers: bf16 implicit-conv tiles of at most 64x64 outputs, bf16 weight-gradient tiles of two k-major operands;
+//   - one LDS buffer behind one register stage (store step t, barrier, load step t+1, multiply): everything else.
+// The pipelines that were measured and lost are in the git history; DESIGN.md keeps their figures.
 //
 //   T = bf16_t : v_mfma_f32_16x16x32_bf16 (fp32 accumulate)
 //   T = float  : v_mfma_f32_16x16x4_f32   (exact fp32, the parity mode)
@@ -26,56 +29,7 @@
 
 namespace mg {
 
-
 constexpr int NTHREADS = 256;
-// K-loop pipeline (build-time): tiles of at most MG_DB_MAX_TILE outputs double-buffer LDS (one barrier
-// per K step) when two stages fit 64 KiB; MG_NSTAGE register stages in that mode.
-#ifndef MG_DB_MAX_TILE
-#define MG_DB_MAX_TILE 0  // measured: double buffering lost to the occupancy it costs (v0-v3 A/B)
-#endif
-#ifndef MG_NSTAGE
-#define MG_NSTAGE 1
-#endif
-// LDS-DMA (buffer_load ... lds) staging for bf16 KC x KC tiles
-// epilogue staging synchronised per block (1) or per wave (0: each wave owns its staging band)
-#ifndef MG_EPI_BLOCK_SYNC
-#define MG_EPI_BLOCK_SYNC 0
-#endif
-// single LDS buffer with two register stages (prefetch distance two K steps) for tiles of at most
-// MG_SB2_MAX_TILE outputs
-#ifndef MG_SB2_MAX_TILE
-#define MG_SB2_MAX_TILE 0
-#endif
-// raise the wave priority over the K step's MFMA phase (A/B switch; MI355X_MICROARCH.md: static priority)
-#ifndef MG_EPI_PREFETCH
-#define MG_EPI_PREFETCH 1
-#endif
-#ifndef MG_SETPRIO
-#define MG_SETPRIO 1  // measured: step 9.273 -> 9.245 ms, 4096^3 953 -> 1066 TF/s, D conv1 751 -> 815 TF/s
-#endif
-#ifndef MG_GLDS
-#define MG_GLDS 0  // measured: on par with register staging at C2 (gemm 4096^3 +9%, expert GEMMs -20%)
-#endif
-// LDS-DMA staging for the implicit-conv forward / data-gradient tiles of at most 64 x 64 outputs only (the latency-
-// bound 3x3 modulated convs on 4x4 / 8x8 / 16x16 maps: their per-step VGPR -> LDS stores are the register path's
-// cost; measured round 6 with MG_GLDS on everything: conv8 41.4 -> 35.7 us, conv4 47.7 -> 42.9 us, while the
-// expert GEMMs lost, so the switch is per loader)
-#ifndef MG_GLDS_CONV
-#define MG_GLDS_CONV 1
-#endif
-// LDS-DMA staging for 64 x 64 tiles whose operands are both k-major ("MC": weight gradients, C = A^T B over pixels
-// / tokens): unpadded LDS images swizzled on the source side, the DMAs as asm statements (hipcc treats the
-// ds_read_b64_tr_b16 intrinsic as aliasing any in-flight LDS-DMA and would wait vmcnt(0) before every fragment read)
-#ifndef MG_GLDS_MC
-#define MG_GLDS_MC 1
-#endif
-// LDS stages of the LDS-DMA pipeline: the loads of step t + STAGES - 1 are in flight while step t is multiplied.
-// 3 runs one barrier per step (step t + 2 issued after step t's barrier); measured slower on every 64^2 conv tile
-// (conv 3x3 at 8^2 35.7 -> 43.4 us, the 16^2 weight gradient 46.9 -> 61.6 us, step 8.10 -> 8.29 ms, same box): the
-// third 16 KiB stage costs more resident blocks than the deeper prefetch and the saved barrier give back
-#ifndef MG_GLDS_STAGES
-#define MG_GLDS_STAGES 2
-#endif
 
 template <typename T> struct Frag;
 template <> struct Frag<bf16_t> { static constexpr int PAD = 8; };
@@ -152,9 +106,11 @@ template <typename V> MG_DEV V bload(rsrc_t r, uint32_t voff, uint32_t soff) {
 MG_DEV void bload_lds(rsrc_t r, uint32_t voff, uint32_t soff, void* lds) {
   __builtin_amdgcn_raw_ptr_buffer_load_lds(r, (__attribute__((address_space(3))) void*)lds, 16, voff, soff, 0, 0);
 }
-// The same DMA as an asm statement, for the MC images (see MG_GLDS_MC): raw descriptor words (as make_rsrc), M0 saved
-// and restored inside the statement; s_nop 4 covers a descriptor / soffset SGPR just written by v_readfirstlane,
-// s_nop 0 the M0 write before the DMA (cdna_hip_programming.md §5.7).  Waited for by the kernel's counted vmcnt.
+// The same DMA as an asm statement, for the MC images (hipcc treats the ds_read_b64_tr_b16 intrinsic that reads them
+// as aliasing any in-flight LDS-DMA and would wait vmcnt(0) before every fragment read): raw descriptor words (as
+// make_rsrc), M0 saved and restored inside the statement; s_nop 4 covers a descriptor / soffset SGPR just written by
+// v_readfirstlane, s_nop 0 the M0 write before the DMA (cdna_hip_programming.md §5.7).  Waited for by the kernel's
+// counted vmcnt.
 typedef int i32x4_t __attribute__((ext_vector_type(4)));
 MG_DEV i32x4_t dma_desc(const void* p) {
   const uint64_t a = reinterpret_cast<uint64_t>(p);
@@ -826,9 +782,9 @@ MG_DEV bf16x8_t mc_frag_bf16(const bf16_t* img, int ld, int kr0, int c0, int lan
   return __builtin_bit_cast(bf16x8_t, r);
 }
 
-// MG_GLDS_MC images (64 columns = 128-B rows, unpadded): 16-B chunk c of k-row k stored at chunk c ^ swz64(k).  Rows
-// alternate 32-bank halves; the four same-parity rows of one 32-lane half of a transposed read (k = 8g + q) get
-// distinct chunk pairs.
+// LDS-DMA images of an MC operand (gemm_tile, GMC).  64 columns (128-B rows, unpadded): 16-B chunk c of k-row k
+// stored at chunk c ^ swz64(k).  Rows alternate 32-bank halves; the four same-parity rows of one 32-lane half of a
+// transposed read (k = 8g + q) get distinct chunk pairs.
 // 128 columns (256-B rows, every row on the same banks): the eight rows of a 32-lane half get distinct chunk pairs
 // of the 16.
 MG_DEV constexpr int swz64(int k) { return (((k >> 1) & 1) | (((k >> 3) & 1) << 1)) << 1; }
@@ -869,7 +825,7 @@ MG_DEV void epi_tile(const f32x4_t (&acc)[BM / 32][BN / 32], void* smem, const E
   constexpr int NE = (2 * WN + 63) / 64;
   // PF: instantiated for the expert GEMMs only (turned on for every tile it cost the step 0.18 ms: code size /
   // register allocation of the other kernels); bf16 operands only (fp32 ones spilled)
-  constexpr bool kPf = PF && MG_EPI_PREFETCH && EP::OV == 1 && FM * NE * 4 <= 32;
+  constexpr bool kPf = PF && EP::OV == 1 && FM * NE * 4 <= 32;
   const bool pfp = kPf && ep.vec_ok && ep.pf_kind() != 0;
   typename EP::Pf pf[kPf ? FM : 1][kPf ? NE : 1];
   if constexpr (kPf) if (pfp) {
@@ -906,14 +862,14 @@ MG_DEV void epi_tile(const f32x4_t (&acc)[BM / 32][BN / 32], void* smem, const E
   __syncthreads();
 #pragma unroll
   for (int i = 0; i < FM; ++i) {
-    if (MG_EPI_BLOCK_SYNC) __syncthreads();
-    else { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
 #pragma unroll
     for (int j = 0; j < FN; ++j)
 #pragma unroll
       for (int r = 0; r < 4; ++r) cs[(fq * 4 + r) * CSP + j * 16 + fr] = acc[i][j][r];
-    if (MG_EPI_BLOCK_SYNC) __syncthreads();
-    else { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); }
+    __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront");
+    __builtin_amdgcn_wave_barrier();
     const int mb = m0 + wm * WM + i * 16, nb = n0 + wn * WN;
     if (kPf && pfp) {
 #pragma unroll
@@ -1005,13 +961,13 @@ MG_DEV void gemm_tile(const AL& A, const BL& B, const EP& ep, int m0, int n0, in
   typedef typename VecOf<T>::type vec_t;
   // LT: element type of the LDS images (X3: bf16 hi / lo images of the fp32 operands, bf16 tile geometry)
   typedef typename std::conditional<X3, bf16_t, T>::type LT;
-  constexpr int TBK = tile_bk<T, X3, BM, BN>();
+  constexpr int TBK = tile_bk<T, X3>();
   constexpr int LDK = TBK + Tile<LT>::PADK;
-  // LDS-DMA staging of two MC operands (MG_GLDS_MC): unpadded, source-swizzled images
+  // LDS-DMA staging of two k-major ("MC") operands (weight gradients C = A^T B): unpadded, source-swizzled images
   constexpr bool GMC = [] {
     if constexpr (!A_KC && !B_KC)
-      return MG_GLDS_MC && !X3 && sizeof(T) == 2 && BM == BN && (BM == 64 || BM == 128) && TBK == 64 &&
-             has_gldsmc<AL>::value && has_gldsmc<BL>::value;
+      return !X3 && sizeof(T) == 2 && BM == BN && (BM == 64 || BM == 128) && TBK == 64 && has_gldsmc<AL>::value &&
+             has_gldsmc<BL>::value;
     else return false;
   }();
   constexpr int PADMC = GMC ? 0 : Tile<LT>::PADM;
@@ -1024,25 +980,26 @@ MG_DEV void gemm_tile(const AL& A, const BL& B, const EP& ep, int m0, int n0, in
   constexpr int A_VPT = BM * TBK / VEC / NTHREADS;
   constexpr int B_VPT = BN * TBK / VEC / NTHREADS;
   static_assert(A_VPT >= 1 && B_VPT >= 1, "tile too small for 256 threads");
-  // LDS: NBUF stages of (A tile, B tile), reused by the epilogue to stage accumulators.  Double
-  // buffering (with a second register stage) when two stages fit the 64 KiB static limit.
+  // LDS: NBUF stages of (A tile, B tile), reused by the epilogue to stage accumulators.
   // X3: (A_hi, A_lo, B_hi, B_lo) images in one stage
   constexpr int STAGE = (X3 ? 2 : 1) * (A_ELEMS + B_ELEMS);
-  // LDS-DMA staging (bf16, both operands k-contiguous without transforms): two LDS stages, no registers
+  // LDS-DMA staging of two k-contiguous operands: the implicit-conv forward / data-gradient tiles of at most 64 x 64
+  // outputs only (the latency-bound 3x3 modulated convs on 4x4 / 8x8 / 16x16 maps: their per-step VGPR -> LDS stores
+  // are the register path's cost).  Measured with LDS-DMA on every KC x KC tile: conv8 41.4 -> 35.7 us, conv4 47.7 ->
+  // 42.9 us, gemm 4096^3 +9 %, but the expert GEMMs -20 % and the C2 step on par, so the selection is per loader.
   constexpr bool GLDS_SEL = [] {
-    if constexpr (A_KC && B_KC) return MG_GLDS || (MG_GLDS_CONV && AL::kConv && BM * BN <= 64 * 64);
+    if constexpr (A_KC && B_KC) return AL::kConv && BM * BN <= 64 * 64;
     else return false;
   }();
-  constexpr int GSTAGES = MG_GLDS ? 2 : MG_GLDS_STAGES;
+  // bf16, no loader transforms, two stages within 64 KiB
   constexpr bool GLDS = [] {
     if constexpr (A_KC && B_KC)
-      return GLDS_SEL && !X3 && sizeof(T) == 2 && AL::kGlds && BL::kGlds && GSTAGES * STAGE * (int)sizeof(T) <= 65536;
+      return GLDS_SEL && !X3 && sizeof(T) == 2 && AL::kGlds && BL::kGlds && 2 * STAGE * (int)sizeof(T) <= 65536;
     else return GMC;
   }();
-  constexpr int NBUF = GLDS ? (GSTAGES * STAGE * (int)sizeof(LT) <= 65536 ? GSTAGES : 2)
-                            : ((!X3 && 2 * STAGE * (int)sizeof(T) <= 65536 && BM * BN <= MG_DB_MAX_TILE) ? 2 : 1);
-  constexpr bool SB2 = NBUF == 1 && !X3 && BM * BN <= MG_SB2_MAX_TILE;
-  constexpr int NS = NBUF == 2 ? MG_NSTAGE : (SB2 ? 2 : 1);
+  // (a second LDS buffer on the register path lost to the occupancy it costs)
+  constexpr int NBUF = GLDS ? 2 : 1;
+  static_assert(NBUF * STAGE * (int)sizeof(LT) <= 65536, "LDS stages exceed 64 KiB");
   __shared__ __attribute__((aligned(16))) LT smem[NBUF * STAGE];
   static_assert(4 * 16 * (WN + 4) * 4 <= (int)sizeof(LT) * STAGE, "epilogue staging does not fit");
 
@@ -1056,6 +1013,7 @@ MG_DEV void gemm_tile(const AL& A, const BL& B, const EP& ep, int m0, int n0, in
   typename AL::Slot as_[A_VPT];
   typename BL::Slot bs_[B_VPT];
   int a_r[A_VPT], a_k[A_VPT], b_r[B_VPT], b_k[B_VPT];
+  // (A and B spelled apart on purpose: through a shared helper hipcc formed the LDS-DMA chunk offsets differently.)
   // GLDS: wave-instruction i of wave w fills LDS rows (4i + w) * 8 .. +8 (1 KiB, lane order); lane L takes
   // row +(L >> 3) and stores physical chunk L & 7, so it loads logical chunk (L & 7) ^ (row & 7) (the swizzle
   // moves to the source address; fragment reads use kc_off unchanged).
@@ -1094,28 +1052,27 @@ MG_DEV void gemm_tile(const AL& A, const BL& B, const EP& ep, int m0, int n0, in
     dB = B.desc();
   }
 
-  // NS register stages: the loads of K step t + NS are issued while step t is multiplied
-  vec_t ra[NS][A_VPT], rb[NS][B_VPT];
-  // issue the buffer loads of K step k0 into register stage R (TAIL: the step reaches past kend)
-  auto gload = [&](auto R, int k0, auto tail) {
-    constexpr int r = decltype(R)::value;
+  // the register stage (unused by the LDS-DMA loop): the loads of K step t + 1 are issued while step t is multiplied
+  vec_t ra[A_VPT], rb[B_VPT];
+  // issue the buffer loads of K step k0 into the register stage (tail: the step reaches past kend)
+  auto gload = [&](int k0, auto tail) {
     constexpr bool TL = decltype(tail)::value;
 #pragma unroll
-    for (int i = 0; i < A_VPT; ++i) ra[r][i] = A.template load<TL, TBK>(rA, as_[i], k0, kend);
+    for (int i = 0; i < A_VPT; ++i) ra[i] = A.template load<TL, TBK>(rA, as_[i], k0, kend);
 #pragma unroll
-    for (int i = 0; i < B_VPT; ++i) rb[r][i] = B.template load<TL, TBK>(rB, bs_[i], k0, kend);
+    for (int i = 0; i < B_VPT; ++i) rb[i] = B.template load<TL, TBK>(rB, bs_[i], k0, kend);
   };
-  auto gload_any = [&](auto R, int k0) {
-    if (k0 + TBK <= kend) gload(R, k0, std::false_type{});
-    else gload(R, k0, std::true_type{});
+  auto gload_any = [&](int k0) {
+    if (k0 + TBK <= kend) gload(k0, std::false_type{});
+    else gload(k0, std::true_type{});
   };
-  // register stage R (K step k0) -> LDS buffer (As, Bs)
-  auto sstore = [&](auto R, int k0, LT* As, LT* Bs) {
-    constexpr int r = decltype(R)::value;
-    if constexpr (X3) {
-      // fp32 vector -> bf16 hi = rn(v), lo = rn(v - hi); the 4 elements land as 8-byte runs in the hi and lo
-      // images (KC: half a 16-B chunk of the swizzled row; MC: 4 columns, the 16-column swizzle keeps them whole)
-      auto split_store = [&](const f32x4_t& v, LT* hi_img, LT* lo_img, int off) {
+  // the register stage (K step k0) -> LDS buffer (As, Bs)
+  auto sstore = [&](int k0, LT* As, LT* Bs) {
+    // one vector to element `off` of an operand's image.  X3: fp32 vector -> bf16 hi = rn(v), lo = rn(v - hi); the 4
+    // elements land as 8-byte runs at the same offset of the hi and lo images (KC: half a 16-B chunk of the
+    // swizzled row; MC: 4 columns, the 16-column swizzle keeps them whole)
+    auto put = [&](const vec_t& v, LT* img, LT* lo_img, int off) {
+      if constexpr (X3) {
         typedef unsigned short u16x4 __attribute__((ext_vector_type(4)));
         u16x4 h, l;
 #pragma unroll
@@ -1123,39 +1080,23 @@ MG_DEV void gemm_tile(const AL& A, const BL& B, const EP& ep, int m0, int n0, in
           h[j] = f2bf(v[j]);
           l[j] = f2bf(v[j] - bf2f(h[j]));
         }
-        *reinterpret_cast<u16x4*>(&hi_img[off]) = h;
+        *reinterpret_cast<u16x4*>(&img[off]) = h;
         *reinterpret_cast<u16x4*>(&lo_img[off]) = l;
-      };
-#pragma unroll
-      for (int i = 0; i < A_VPT; ++i) {
-        vec_t v = ra[r][i];
-        A.fix(as_[i], k0, v);
-        const int off = A_KC ? kc_off<LT>(a_r[i], a_k[i], LDK) : a_k[i] * LDA + (a_r[i] ^ mc_swz<LT>(a_k[i]));
-        split_store(v, As, As + A_ELEMS, off);
+      } else {
+        *reinterpret_cast<vec_t*>(&img[off]) = v;
       }
-#pragma unroll
-      for (int i = 0; i < B_VPT; ++i) {
-        vec_t v = rb[r][i];
-        B.fix(bs_[i], k0, v);
-        const int off = B_KC ? kc_off<LT>(b_r[i], b_k[i], LDK) : b_k[i] * LDB + (b_r[i] ^ mc_swz<LT>(b_k[i]));
-        split_store(v, Bs, Bs + B_ELEMS, off);
-      }
-      return;
-    } else {
+    };
 #pragma unroll
     for (int i = 0; i < A_VPT; ++i) {
-      vec_t v = ra[r][i];
+      vec_t v = ra[i];
       A.fix(as_[i], k0, v);
-      if constexpr (A_KC) *reinterpret_cast<vec_t*>(&As[kc_off<T>(a_r[i], a_k[i], LDK)]) = v;
-      else *reinterpret_cast<vec_t*>(&As[a_k[i] * LDA + (a_r[i] ^ mc_swz<T>(a_k[i]))]) = v;
+      put(v, As, As + A_ELEMS, A_KC ? kc_off<LT>(a_r[i], a_k[i], LDK) : a_k[i] * LDA + (a_r[i] ^ mc_swz<LT>(a_k[i])));
     }
 #pragma unroll
     for (int i = 0; i < B_VPT; ++i) {
-      vec_t v = rb[r][i];
+      vec_t v = rb[i];
       B.fix(bs_[i], k0, v);
-      if constexpr (B_KC) *reinterpret_cast<vec_t*>(&Bs[kc_off<T>(b_r[i], b_k[i], LDK)]) = v;
-      else *reinterpret_cast<vec_t*>(&Bs[b_k[i] * LDB + (b_r[i] ^ mc_swz<T>(b_k[i]))]) = v;
-    }
+      put(v, Bs, Bs + B_ELEMS, B_KC ? kc_off<LT>(b_r[i], b_k[i], LDK) : b_k[i] * LDB + (b_r[i] ^ mc_swz<LT>(b_k[i])));
     }
   };
 
@@ -1262,15 +1203,20 @@ MG_DEV void gemm_tile(const AL& A, const BL& B, const EP& ep, int m0, int n0, in
       }
     }
   };
-  using I0 = std::integral_constant<int, 0>;
-  using I1 = std::integral_constant<int, 1>;
 
   if constexpr (GLDS) {
     // LDS-DMA, two stages: step t+1's loads are issued before step t is multiplied; a counted vmcnt
     // retires only step t's (issued earlier), a raw barrier publishes them, and a second barrier keeps
     // step t+2's DMA from overwriting the buffer while another wave still reads it.
-    static_assert((NBUF - 1) * (A_VPT + B_VPT) < 64, "vmcnt range");
-    static_assert(NBUF == 2 || NBUF == 3, "LDS-DMA pipeline: 2 or 3 stages");
+    // Two stages, not three: a three-stage ring with one barrier per step (step t+2 issued after step t's barrier)
+    // measured slower on every 64^2 conv tile (conv 3x3 at 8^2 35.7 -> 43.4 us, the 16^2 weight gradient 46.9 ->
+    // 61.6 us, step 8.10 -> 8.29 ms, same box): the third 16 KiB stage costs more resident blocks than the deeper
+    // prefetch and the saved barrier give back.
+    constexpr int PER = A_VPT + B_VPT;  // DMA instructions per step
+    static_assert((NBUF - 1) * PER < 64, "vmcnt range");
+    // the DMAs of K step k0 into stage `buf`: instruction i of this wave lands 1 KiB at element (i * 4 + wid) * 512 of
+    // its operand's image (KC: 8 rows of LDK = 64; MC: see the load slots).  (Spelled per tail on purpose: over a tail
+    // tag, as gload is, the LdMCConvS1 weight-gradient kernels came out with one instruction scheduled elsewhere.)
     auto issue = [&](int k0, LT* buf) {
       if constexpr (GMC) {
         if (k0 + TBK <= kend) {
@@ -1302,24 +1248,7 @@ MG_DEV void gemm_tile(const AL& A, const BL& B, const EP& ep, int m0, int n0, in
       }
     };
     const int nsteps = kend > kbeg ? (kend - kbeg + TBK - 1) / TBK : 0;
-    constexpr int PER = A_VPT + B_VPT;  // DMA instructions per step
-    if constexpr (NBUF == 3) {
-      // three stages, ONE barrier per step: step t + 2 is issued after the barrier of step t, into the stage step
-      // t - 1 read (every wave finished step t - 1 before arriving at that barrier); before it, a counted vmcnt
-      // retires this wave's DMA of step t (step t + 1's may stay in flight)
-      if (nsteps > 0) issue(kbeg, smem);
-      if (nsteps > 1) issue(kbeg + TBK, smem + STAGE);
-      for (int t = 0; t < nsteps; ++t) {
-        LT* cur = smem + (t % 3) * STAGE;
-        if (t + 1 < nsteps) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER) : "memory");
-        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's reads of step t - 1 have landed (WAR)
-        __builtin_amdgcn_s_barrier();
-        if (t + 2 < nsteps) issue(kbeg + (t + 2) * TBK, smem + ((t + 2) % 3) * STAGE);
-        compute(cur, cur + A_ELEMS);
-      }
-    } else {
-    // two stages: step t + 1 is in flight while step t is multiplied
+    // NBUF - 1 = 1 step ahead (a loop on purpose: as a plain statement it changed hipcc's register allocation)
 #pragma unroll
     for (int p = 0; p < NBUF - 1; ++p)
       if (p < nsteps) issue(kbeg + p * TBK, smem + p * STAGE);
@@ -1329,8 +1258,6 @@ MG_DEV void gemm_tile(const AL& A, const BL& B, const EP& ep, int m0, int n0, in
       if (ahead < nsteps) {
         issue(kbeg + ahead * TBK, smem + (ahead % NBUF) * STAGE);
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"((NBUF - 1) * PER) : "memory");
-      } else if (NBUF > 2 && nsteps - 1 - t == 1) {
-        asm volatile("s_waitcnt vmcnt(%0)" ::"n"(PER) : "memory");
       } else {
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       }
@@ -1339,89 +1266,21 @@ MG_DEV void gemm_tile(const AL& A, const BL& B, const EP& ep, int m0, int n0, in
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // this wave's reads of cur have landed (WAR)
       __builtin_amdgcn_s_barrier();
     }
-    }
-  } else if constexpr (NBUF == 2) {
-    // Two LDS buffers, one barrier per K step.  Step t multiplies LDS[t & 1], then writes the register
-    // stage holding step t+1 into LDS[(t+1) & 1] (last read by step t-1, whose closing barrier freed it)
-    // and refills that stage with step t+1+NS.
-    if (kbeg < kend) {
-      gload_any(I0{}, kbeg);
-      if constexpr (NS == 2)
-        if (kbeg + TBK < kend) gload_any(I1{}, kbeg + TBK);
-      sstore(I0{}, kbeg, smem, smem + A_ELEMS);
-      if (kbeg + NS * TBK < kend) gload_any(I0{}, kbeg + NS * TBK);
-      __syncthreads();
-    }
-    // one multiply per loop body (so the accumulators keep their registers); with two register stages
-    // the parity of the stage being written back is a uniform branch between two static-index copies
-    const int nsteps = kend > kbeg ? (kend - kbeg + TBK - 1) / TBK : 0;
-    for (int t = 0; t < nsteps; ++t) {
-      const int k0 = kbeg + t * TBK;
-      const LT* cur = smem + (t & 1) * STAGE;
-      compute(cur, cur + A_ELEMS);
-      const int kn = k0 + TBK;
-      if (kn < kend) {
-        LT* nxt = smem + ((t + 1) & 1) * STAGE;
-        if (NS == 1 || (t & 1)) {
-          sstore(I0{}, kn, nxt, nxt + A_ELEMS);
-          if (kn + NS * TBK < kend) gload_any(I0{}, kn + NS * TBK);
-        } else if constexpr (NS == 2) {
-          sstore(I1{}, kn, nxt, nxt + A_ELEMS);
-          if (kn + NS * TBK < kend) gload_any(I1{}, kn + NS * TBK);
-        }
-      }
-      __syncthreads();
-    }
-  } else if constexpr (SB2) {
-    // one LDS buffer, two register stages: the loads of step t+2 are issued right after step t's registers went
-    // to LDS, so two multiplies (not one) cover each load's latency.  Straight-line body over two K steps with
-    // tail-safe loads throughout (past kend they read zeros), so no branch splits the load stream and the
-    // compiler's vmcnt waits count only the older stage.
-    LT* const As = smem;
-    LT* const Bs = smem + (X3 ? 2 : 1) * A_ELEMS;
-    using TT = std::true_type;
-    // scheduling barriers pin the issue order (stage 0 before stage 1, each reload before its multiply) so on
-    // both paths into the loop head stage 0 is the older stage and its wait is vmcnt(#stage-1 loads), not 0
-    gload(I0{}, kbeg, TT{});
-    __builtin_amdgcn_sched_barrier(0);
-    gload(I1{}, kbeg + TBK, TT{});
-    __builtin_amdgcn_sched_barrier(0);
-    // whole pairs of K steps in the loop (one exit: the waits at its head see one load order), an odd last
-    // step after it
-    int k0 = kbeg;
-    for (; k0 + TBK < kend; k0 += 2 * TBK) {
-      __syncthreads();
-      sstore(I0{}, k0, As, Bs);
-      __syncthreads();
-      gload(I0{}, k0 + 2 * TBK, TT{});
-      __builtin_amdgcn_sched_barrier(0);
-      compute(As, Bs);
-      __syncthreads();
-      sstore(I1{}, k0 + TBK, As, Bs);
-      __syncthreads();
-      gload(I1{}, k0 + 3 * TBK, TT{});
-      __builtin_amdgcn_sched_barrier(0);
-      compute(As, Bs);
-    }
-    if (k0 < kend) {
-      __syncthreads();
-      sstore(I0{}, k0, As, Bs);
-      __syncthreads();
-      compute(As, Bs);
-    }
   } else {
     // one LDS buffer, one register stage: store, barrier, prefetch the next step, multiply
     LT* const As = smem;
     LT* const Bs = smem + (X3 ? 2 : 1) * A_ELEMS;
-    if (kbeg < kend) gload_any(I0{}, kbeg);
+    if (kbeg < kend) gload_any(kbeg);
     for (int k0 = kbeg; k0 < kend; k0 += TBK) {
       __syncthreads();
-      sstore(I0{}, k0, As, Bs);
+      sstore(k0, As, Bs);
       __syncthreads();
-      if (k0 + TBK < kend) gload_any(I0{}, k0 + TBK);
-      if (MG_SETPRIO) __builtin_amdgcn_s_setprio(1);  // the multiply phase first in the SIMD's issue arbitration
+      if (k0 + TBK < kend) gload_any(k0 + TBK);
+      // the multiply phase first in the SIMD's issue arbitration (measured against no priority change: step 9.273 ->
+      // 9.245 ms, 4096^3 953 -> 1066 TF/s, D conv1 751 -> 815 TF/s)
+      __builtin_amdgcn_s_setprio(1);
       compute(As, Bs);
-      if (MG_SETPRIO) __builtin_amdgcn_s_setprio(0);
+      __builtin_amdgcn_s_setprio(0);
     }
   }
 
@@ -1441,11 +1300,10 @@ MG_DEV void gemm_tile(const AL& A, const BL& B, const EP& ep, int m0, int n0, in
   epi_tile<BM, BN, EP, PF>(acc, smem, ep, m0, n0, Mloc, N, mrow_base);
 }
 
-
 // TAG only names the instantiation (1 = MoE expert GEMMs) so profiles can attribute its dispatches.
 template <typename T, int BM, int BN, bool A_KC, bool B_KC, class AL, class BL, class EP, int TAG = 0, bool X3 = false>
 __global__ __launch_bounds__(NTHREADS) void gemm_kernel(AL A, BL B, EP ep, int M, int N, int K, int kchunk, Grouping grp) {
-  constexpr int TBK = tile_bk<T, X3, BM, BN>();
+  constexpr int TBK = tile_bk<T, X3>();
   // ---- resolve tile / group ----
   int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
   if (((grp.mode == 0 || grp.mode == 1) && grp.swz && (grp.swz == 1 || gridDim.z > 1)) || (grp.mode == 2 && grp.swz)) {
@@ -1553,7 +1411,7 @@ __global__ __launch_bounds__(NTHREADS) void gemm_batch_kernel(BatchArgs<TO, AL, 
 template <typename T, int BM, int BN, bool A_KC, bool B_KC, int TAG = 0, bool X3 = false, class AL, class BL, class EP>
 inline void launch_gemm(const AL& A, const BL& B, const EP& ep, int M, int N, int K, int splits, Grouping grp,
                         int max_tiles_m, hipStream_t st) {
-  constexpr int TBK = tile_bk<T, X3, BM, BN>();
+  constexpr int TBK = tile_bk<T, X3>();
   int kchunk = K;
   if (grp.mode != 2 && splits > 1) kchunk = ((K + splits - 1) / splits + TBK - 1) / TBK * TBK;
   if (grp.mode != 2) splits = (K + kchunk - 1) / kchunk;

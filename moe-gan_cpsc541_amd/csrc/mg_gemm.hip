@@ -260,7 +260,7 @@ int run_batch(int n, const mg_gemm_desc* d, hipStream_t st) {
     // blocks.  Opt-in (tuning slot 21 = block target): split K into fp32 slabs, then one batched reduction applies
     // each real epilogue.  The batched GEMMs halve (12.9 -> 7.1 us average) but the reduction launches cost what
     // that saves: 8.844 / 8.826 ms per step with / without at 512 blocks (same box, three rounds), so off.
-    constexpr int TBK = tile_bk<T, X3, 64, 64>();
+    constexpr int TBK = tile_bk<T, X3>();
     const int bs = g_mg_tune[MG_TUNE_BATCH_SPLIT];
     int S = 1;
     if (bs > 1) {
@@ -487,7 +487,7 @@ template <typename T, int BM, int BN, bool XF = false, bool BG = false>
 bool run_wgrad_slabs(const void* gy, int64_t ldg, const void* x, int B, int H, int W, int Cin, const float* sc,
                      int Cout, int KH, int KW, int stride, int pad, float* gw, int splits, hipStream_t st,
                      float* bias_out = nullptr) {
-  constexpr int TBK = tile_bk<T, false, BM, BN>();
+  constexpr int TBK = tile_bk<T, false>();
   int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
   int P = B * OH * OW, N = KH * KW * Cin;
   int kchunk = ((P + splits - 1) / splits + TBK - 1) / TBK * TBK;
@@ -932,7 +932,7 @@ extern "C" int mg_conv2d_dgrad_s2(int dtype, const void* g, int B, int OH, int O
   with_types(false, dtype, out_dtype, [&](auto t, auto to, auto) {
     using T = decltype(t);
     using TO = decltype(to);
-    if (Cg < max_tile_bk<T>()) run_dgrad_s2<T, TO, true>(g, B, OH, OW, Cg, wcls, Cin, out, ldo, ep, st);
+    if (Cg < tile_bk<T, false>()) run_dgrad_s2<T, TO, true>(g, B, OH, OW, Cg, wcls, Cin, out, ldo, ep, st);
     else run_dgrad_s2<T, TO, false>(g, B, OH, OW, Cg, wcls, Cin, out, ldo, ep, st);
   });
   return mg_check_launch("mg_conv2d_dgrad_s2");

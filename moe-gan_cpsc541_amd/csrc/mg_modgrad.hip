@@ -44,7 +44,7 @@ const char* refuse(int dtype, int gx_dtype, int k, int B, int H, int W, int Cg, 
     return "s / x / gx must be 16-byte aligned with pitches that keep rows so";
   if (k == 3) {
     if (!pow2(H) || !pow2(W) || !pow2(Cg)) return "3x3: H, W and the gradient's channels must be powers of two";
-    if (Cg < max_tile_bk_of(bf16)) return "3x3: gradient channels below one K step";
+    if (Cg < tile_bk_of(bf16, false)) return "3x3: gradient channels below one K step";
   }
   const Plan p = plain_plan(bf16, k, B, H, W, Cg, Cin);
   if (p.route == ROUTE_DIRECT) return "the unfused conv runs direct";

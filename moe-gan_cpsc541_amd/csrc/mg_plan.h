@@ -44,27 +44,10 @@ template <> struct Tile<bf16_t> { static constexpr int BK = 64, PADK = 0, PADM =
 template <> struct Tile<float> { static constexpr int BK = 32, PADK = 4, PADM = 16; };
 
 // K step of a GEMM instantiation: X3 (fp32 operands multiplied as split bf16, hi*hi + hi*lo + lo*hi) stages its
-// tiles as bf16 images, so it takes the bf16 step
-// MG_BK_SMALL: the K step of bf16 tiles of at most 64 x 64 outputs (A/B build switch; 64 = the common step).  A
-// 128-deep step doubles the bytes each of those latency-bound blocks keeps in flight per barrier.
-#ifndef MG_BK_SMALL
-#define MG_BK_SMALL 64
-#endif
-// MG_X3_BK: the K step of the split-bf16 fp32 tiles (64 x 64 only; the small-M prefix / demodulation GEMMs are
-// serial chains of K steps on few tiles, so a deeper step halves their chain; 64 = the bf16 step)
-#ifndef MG_X3_BK
-#define MG_X3_BK 64
-#endif
-constexpr int tile_bk_of(bool bf16, bool x3, int BM, int BN) {
-  return x3 ? (BM * BN <= 64 * 64 ? MG_X3_BK : Tile<bf16_t>::BK)
-            : (bf16 && BM * BN <= 64 * 64) ? MG_BK_SMALL : bf16 ? Tile<bf16_t>::BK : Tile<float>::BK;
-}
-template <typename T, bool X3, int BM = 128, int BN = 128> constexpr int tile_bk() {
-  return tile_bk_of(sizeof(T) == 2, X3, BM, BN);
-}
-// the largest K step any tile of the dtype uses (the implicit-conv loaders' "one tap per K step" test needs Cin >= it)
-constexpr int max_tile_bk_of(bool bf16) { return std::max(tile_bk_of(bf16, false, 64, 64), tile_bk_of(bf16, false, 128, 128)); }
-template <typename T> constexpr int max_tile_bk() { return max_tile_bk_of(sizeof(T) == 2); }
+// tiles as bf16 images, so it takes the bf16 step.  The step does not depend on the output tile (the implicit-conv
+// loaders' "one tap per K step" test needs Cin >= it, whatever tile the call lands on).
+constexpr int tile_bk_of(bool bf16, bool x3) { return (x3 || bf16) ? Tile<bf16_t>::BK : Tile<float>::BK; }
+template <typename T, bool X3> constexpr int tile_bk() { return tile_bk_of(sizeof(T) == 2, X3); }
 
 // stride-1 "same" convolution whose weight gradient can use the cheap-address column loader (LdMCConvS1)
 inline bool wgrad_s1(int H, int W, int KH, int KW, int stride, int pad, int tbk) {
@@ -144,7 +127,7 @@ inline Plan plan_gemm(bool bf16, bool x3, int M, int N, int K, GemmEpi e, int sp
     }
   }
   if (K == 0) splits = 1;
-  const int tbk = tile_bk_of(bf16, x3, 64, 64);
+  const int tbk = tile_bk_of(bf16, x3);
   int slabs = 0;
   if (splits > 1 && mg_det()) {  // deterministic mode: exactly that many fp32 slabs + one fixed-order reduction, not
     if (!e.xf) slabs = std::min(splits, cdiv(K, tbk));  // atomics; one launch in K order where slabs cannot be had
@@ -195,7 +178,7 @@ inline Plan plan_conv_fwd(bool bf16, int B, int H, int W, int Cin, int Cout, int
   const int OH = (H + 2 * pad - KH) / stride + 1, OW = (W + 2 * pad - KW) / stride + 1;
   const int64_t M = (int64_t)B * OH * OW;
   const int K = KH * KW * Cin;
-  const bool small_c = Cin < max_tile_bk_of(bf16);
+  const bool small_c = Cin < tile_bk_of(bf16, false);
   const Plan one = tiles_plan(conv_tile(bf16, has_in_scale, small_c, M, Cout, K), 1, small_c);
   // 32-channel 3x3 convs on small maps (offset heads): direct, halo tiles in LDS
   if (bf16 && !has_in_scale && !atomic && !direct_declined &&
@@ -209,7 +192,7 @@ inline Plan plan_conv_fwd(bool bf16, int B, int H, int W, int Cin, int Cout, int
   // fp32 slabs over ~1024 blocks of >= 8 K steps each and apply the epilogue in the reduction.  Narrow outputs
   // (Cout <= 32) use 128 x 32 tiles (no MFMA columns wasted).
   const TileMN st = bf16 && Cout <= 32 ? TileMN{128, 32} : TileMN{64, 64};
-  const int tbk = tile_bk_of(bf16, false, st.BM, st.BN), ksteps = K / tbk;
+  const int tbk = tile_bk_of(bf16, false), ksteps = K / tbk;
   const int64_t tiles = (int64_t)cdiv(M, st.BM) * cdiv(Cout, st.BN);
   if (tiles >= 1024 || ksteps < 16 || atomic || has_in_scale || g_mg_tune[MG_TUNE_NO_SLABS]) return one;
   const int slabs = (int)std::min<int64_t>(cdiv(1024, tiles), ksteps / 8);

@@ -38,7 +38,7 @@ static void check_plan(const Plan& p, bool bf16, bool x3, bool conv, int K) {
   CHECK(p.splits >= 1);
   if (p.route == ROUTE_SLABS) {
     ++g_slabs;
-    const int tbk = tile_bk_of(bf16, x3, p.BM, p.BN);
+    const int tbk = tile_bk_of(bf16, x3);
     CHECK(p.kchunk > 0 && p.kchunk % tbk == 0);
     CHECK(p.splits >= 2);
     CHECK((int64_t)(p.splits - 1) * p.kchunk < K && K <= (int64_t)p.splits * p.kchunk);

@@ -122,7 +122,8 @@ def test_grouped_gemm_and_wgrad(dtype, tol, C):
 def test_grouped_gelu_grad_epilogue(C, H4):
     """The expert backward's gP GEMM (engine_g.moe_bwd): gP = (gG @ W2_e) * GELU'(pre), B = W2 [E, C, H4]
     N-contiguous, bf16.  Its epilogue loads the pre-activation for the whole tile ahead of the band loop
-    (MG_EPI_PREFETCH); ragged groups, an empty group and a partial last tile cover the row guards."""
+    (the expert instantiations' operand prefetch, epi_tile's PF); ragged groups, an empty group and a partial last
+    tile cover the row guards."""
     g = torch.Generator(device=DEV).manual_seed(11)
     E = 4
     counts = [200, 0, 333, 129]

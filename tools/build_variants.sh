@@ -1,7 +1,9 @@
 #!/bin/bash
-# Build A/B variants of libmoegan_hip.so that differ only in mg_gemm.hip compile flags.
+# Build A/B variants of libmoegan_hip.so that differ only in the compile flags of one source.
 #   tools/build_variants.sh name1 "-DFLAG=.." name2 "-DFLAG=.." ...
-# (SRC=<file.hip> varies another source; default mg_gemm.hip)
+# (SRC=<file.hip> names the source; default mg_gemm.hip)
+# The tree keeps no standing set of build switches: an experiment adds its own #ifndef FLAG default to the source
+# it tries, is measured through this script, and the switch leaves again with the verdict.
 # -> moe-gan_cpsc541_amd/moegan_mi/libmoegan_hip_<name>.so  (select with MOEGAN_HIP_LIB=<path>)
 set -e
 cd "$(dirname "$0")/../moe-gan_cpsc541_amd/csrc"
